@@ -2,7 +2,7 @@
 """BiGCN training-step benchmark on MI355X (BASELINE.json metric: propagation-trees/s
 fwd+bwd, batch = 128 trees per GPU, 5000-dim features).
 
-    python bench.py [--gpus N --steps K --warmup W --workload twitter15]
+    python bench.py [--gpus N --steps K --warmup W --workload twitter15] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,6 +12,12 @@ the fused encoder forward, fc + log_softmax + NLL, backward, the DP gradient all
 (N > 1) and the Adam step with the reference's three parameter groups.  Batches are
 cycled from a pool of ``--pool`` distinct batches (each larger than the 256 MiB
 Infinity Cache).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  ``--full``
+adds every other measurement to the line (the dense path, the other DropEdge placement, the
+drop-in loop, the evaluation step, the standalone aggregation and compaction, the host-fed
+legs, the CPU baseline).  ``--dump-outputs DIR`` writes what the last timed step handed its
+caller (loss, gradients, updated parameters, saved activations) as ``DIR/<name>.npy``.
 """
 from __future__ import annotations
 
@@ -232,6 +238,35 @@ def make_pool(wl, rank, pool, device, drop=None):
             b.x = torch.randn(b.x.shape, generator=g, device=device, dtype=xdt)
         out.append(b)
     return out
+
+
+DUMP_ROWS = 16384   # rows kept of each [N, 128] activation (a fixed, seeded sample of larger ones)
+
+
+def dump_outputs(path: str, step_path: str, loss, model, fused):
+    """--dump-outputs: what the caller of the timed path holds after the last timed step, as
+    float32 ``<name>.npy`` files under ``path``: the step's loss, the gradient and the updated
+    value of every parameter and (fused path) the saved pre-relu activations H1 / H2, of which
+    the same DUMP_ROWS seeded rows are kept when there are more.  Under 30 MB in all."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+
+    def save(name, t):
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+    save("loss", loss.reshape(1))
+    grads = fused.grads() if step_path == "fused" else None
+    for name, p in model.named_parameters():
+        save("param." + name, p)
+        g = grads.get(p) if grads is not None else p.grad
+        if g is not None:
+            save("grad." + name, g)
+    if step_path == "fused":
+        for name, h in zip(("H1", "H2"), fused.saved_activations()):
+            n = h.size(0)
+            if n > DUMP_ROWS:
+                rows = np.sort(np.random.default_rng(20250205).choice(n, DUMP_ROWS, replace=False))
+                h = h[torch.as_tensor(rows, device=h.device)]
+            save(name, h)
 
 
 def cpu_threads() -> int:
@@ -521,6 +556,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="twitter15", choices=sorted(WORKLOADS))
     ap.add_argument("--pool", type=int, default=4)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, gradients, updated "
+                         "parameters, saved activations) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other measurement (CPU baseline, dense path, DropEdge placement, "
+                         "drop-in loop, evaluation step, aggregation, compaction, host-fed legs); the "
+                         "options below that select among them apply under --full only")
     ap.add_argument("--cpu-trees", type=int, default=32,
                     help="CPU baseline: trees per step (a bounded sample of the workload, ~1 s per step)")
     ap.add_argument("--cpu-steps", type=int, default=10, help="CPU baseline: timed steps per repeat")
@@ -756,9 +798,11 @@ def main():
         if world > 1:
             dist.all_reduce(v, op=dist.ReduceOp.MAX)
         return {"value": value, "dt": dt, "t_host": t_host, "N_avg": N_avg, "roof": roof, "kernels": kernels,
-                "loss": float(loss.item()), "status": int(v[0]), "invalid_steps": int(v[1])}
+                "loss": float(loss.item()), "loss_tensor": loss, "status": int(v[0]), "invalid_steps": int(v[1])}
 
     main_res = run(args.feat_mode, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, args.path, main_res["loss_tensor"], model, fused)
 
     def fresh_allocator():
         # each comparison leg starts from the caching allocator state a fresh process would
@@ -768,11 +812,11 @@ def main():
         gc.collect()
         torch.cuda.empty_cache()
     dense_res = None
-    if world == 1 and args.feat_mode != "dense" and args.compare_dense:
+    if args.full and world == 1 and args.feat_mode != "dense" and args.compare_dense:
         fresh_allocator()
         dense_res = run("dense", max(3, args.steps // 2), 2)
     drop_res = None
-    if world == 1 and args.path == "fused" and args.compare_dropedge:
+    if args.full and world == 1 and args.path == "fused" and args.compare_dropedge:
         fresh_allocator()
         other = not device_drop                         # the other DropEdge placement
         ctx["pool"] = make_pool(wl, rank, args.pool, dev, (0.0, 0.0) if other else None)
@@ -782,7 +826,7 @@ def main():
         drop_res["where"] = "device" if other else "host_once_untimed"
         ctx["pool"], ctx["fused"] = pool, fused
     dropin_res = None
-    if world == 1 and args.path == "fused" and args.dropin:
+    if args.full and world == 1 and args.path == "fused" and args.dropin:
         # the north_star drop-in form: the reference's loop body verbatim on the per-op
         # modules (gcn_norm/CSR rebuilt every step as GCNConv does), DropEdge applied by the
         # host DataLoader as in the reference (once per pool batch here, untimed)
@@ -809,7 +853,7 @@ def main():
             ctx["ahead"] = None
         ctx["pool"], ctx["path"] = pool, args.path
     eval_res = None
-    if world == 1 and args.path == "fused" and args.eval_path:
+    if args.full and world == 1 and args.path == "fused" and args.eval_path:
         # the reference's per-epoch test loop (BiGCN_Twitter.py:207-222) in the fused form:
         # eval-mode forward + head + NLL mean + argmax / correct count per batch, the next
         # batch prepared on the side lane, no host sync inside the timed loop
@@ -836,14 +880,14 @@ def main():
                             "model(data), nll_loss, argmax, correct count) per pool batch, the next batch "
                             "prepared beside it; no DropEdge, no dropout"}
     agg = None
-    if world == 1 and args.aggregation:
+    if args.full and world == 1 and args.aggregation:
         agg = aggregation_bench(pool[0])
     comp = None
-    if world == 1 and args.path == "fused" and args.feat_mode == "auto":
+    if args.full and world == 1 and args.path == "fused" and args.feat_mode == "auto":
         with torch.cuda.stream(stream):
             comp = compaction_standalone(fused, pool[0], wl)
     staging = None
-    if world == 1 and args.path == "fused" and args.host_fed and args.feat_mode == "auto":
+    if args.full and world == 1 and args.path == "fused" and args.host_fed and args.feat_mode == "auto":
         # same model / optimiser / DropEdge as the headline step (its state continues)
         staging = staging_bench(fused, wl, dev, stream, max(20, args.steps), min(args.warmup, 10),
                                 args.host_fed_workers, args.host_fed_trees)
@@ -851,7 +895,7 @@ def main():
         value, dt, N_avg = main_res["value"], main_res["dt"], main_res["N_avg"]
         roof, kernels, final_loss = main_res["roof"], main_res["kernels"], main_res["loss"]
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("cpu baseline ...")
             cpu = cpu_baseline(wl, args.cpu_trees, args.cpu_steps, args.cpu_warmup, args.cpu_repeats)
         out = {

@@ -11,8 +11,9 @@ through BGCN_LIB) and/or ``NAME=VALUE`` environment overrides the library reads 
 runs as its own child process with its own time limit - reps outermost, so box drift shows
 up as spread rather than as a difference - and prints one line: the bench's trees/s,
 ms/step, the roofline kernel's span and fraction, and the standalone pass's paced /
-unpaced fractions (or the probe's output).  The bench runs light (no CPU baseline, no
-comparison legs) unless --bench-args brings them back.  On the GPU box:
+unpaced fractions (or the probe's output).  The bench runs with --full and every leg that
+has a switch turned off (no CPU baseline, no comparison legs; the standalone pass stays)
+unless --bench-args brings them back.  On a machine with the GPU:
 
     gpurun -- 'python tools/ab.py base BGCN_PREP_LANES=1 --workloads "twitter15 weibo_bf16"'
 """
@@ -76,7 +77,7 @@ def main():
                     if a.probe:
                         cmd = [sys.executable, *shlex.split(a.probe)]
                     else:
-                        cmd = [sys.executable, "bench.py", "--workload", w, *LIGHT, "--steps", str(a.steps),
+                        cmd = [sys.executable, "bench.py", "--workload", w, "--full", *LIGHT, "--steps", str(a.steps),
                                "--warmup", str(a.warmup), *shlex.split(a.bench_args)]
                     try:
                         p = subprocess.run(cmd, cwd=ROOT, env=variant_env(v), capture_output=True, text=True,

@@ -21,9 +21,9 @@ if has bench; then
 for w in $WLS; do
   # the same command without the profiler first: the profiler slows the step (its span of the
   # pass then reads the perturbed step's), so both step times are kept side by side
-  timeout -k 10 300 python bench.py --workload $w $LIGHT > "$OUT/bench_unprofiled_$w.json" 2> "$OUT/unprofiled_$w.log"
+  timeout -k 10 300 python bench.py --workload $w --full $LIGHT > "$OUT/bench_unprofiled_$w.json" 2> "$OUT/unprofiled_$w.log"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$w" -o run -- \
-    python bench.py --workload $w $LIGHT > "$OUT/bench_under_rocprof_$w.json" 2> "$OUT/stats_$w.log"
+    python bench.py --workload $w --full $LIGHT > "$OUT/bench_under_rocprof_$w.json" 2> "$OUT/stats_$w.log"
   python tools/prof.py forms "$OUT/stats_$w/run_kernel_trace.csv" > "$OUT/kernel_forms_$w.txt"
   timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch_$w" -- \
     python bench.py --workload $w $LIGHT --steps 5 --warmup 2 > /dev/null 2> "$OUT/fetch_$w.log"

@@ -17,7 +17,7 @@ timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d "$OUT/timeline
   python tools/trace_probe.py --mode both > "$OUT/timeline.log" 2>&1
 python tools/prof.py timeline "$OUT"/timeline/run_kernel_trace.csv --after k_alu --step 8 > "$OUT/timeline_step.txt"
 python tools/prof.py timeline "$OUT"/timeline/run_kernel_trace.csv --after k_alu --step 20 > "$OUT/timeline_chain_alone.txt"
-timeout -k 10 400 python bench.py > "$OUT/bench_full.json" 2> "$OUT/bench_full.log"
+timeout -k 10 400 python bench.py --full > "$OUT/bench_full.json" 2> "$OUT/bench_full.log"
 echo "full bench done"
 for w in ${WORKLOADS:-weibo_bf16 synth1024_bf16 pheme768 twitter15_tail}; do
   timeout -k 10 200 python bench.py --workload "$w" $LIGHT > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.log"
