@@ -977,7 +977,7 @@ int bigcn_forward_impl(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, hipS
       BGCN_TRY(sparse_prologue(sp, a, w.node_root, s, false));
     if (sparse) {
       timing_begin(0, s);
-      BGCN_TRY(sparse_conv1_gather(sp, w.z1, s, a->rootindex, keep.scale()));
+      BGCN_TRY(sparse_conv1_gather(sp, w.z1, s));
       timing_end(0, s);
     }
     if (dense_launched(a, sp))
@@ -1034,7 +1034,7 @@ static int forward_tail(const bgcn_bigcn_args* a, FusedWs& w, SparseState& sp, K
   BGCN_TRY(spmm_pair(a->td, a->bu, false, N, w.z1, a->h1, a->td_b1, a->bu_b1, BGCN_EPI_NONE, w, s));
   // conv2 lin with the root-extended, relu'd, dropped-out A operand generated in-kernel
   timing_begin(2, s);
-  if (sparse) BGCN_TRY(sparse_conv2(sp, a->h1, a->tree_ptr, a->rootindex, w.z2, keep, s));
+  if (sparse) BGCN_TRY(sparse_conv2(sp, a->h1, w.z2, keep, s));
   if (dense_launched(a, sp)) {
     // bf16 X: the bf16 MFMA (BGCN_GEMM_BF16=0 keeps the f32 MFMA form)
     if (a->x_dtype == BGCN_DTYPE_BF16 && bf16_mfma_ok(a))

@@ -117,16 +117,11 @@ __device__ inline void dw2_body(const TX* __restrict__ X, int64_t ldx, int64_t F
     if (kt + 1 < nk) gload(kb + int64_t(kt + 1) * BK);
     const float* A = &As[buf][h * H + wr * 32 + r32];
     const float* B = &Bs[buf][h * BN + wc * 32 + r32];
-#ifdef BGCN_DW2_ONE_ACC   // A/B build: the single running accumulator of round 5
-#pragma unroll
-    for (int s = 0; s < BK / 2; ++s) acc = mfma32x32x2(A[2 * s * H], B[2 * s * BN], acc);
-#else
     f32x16 tile = {0};
 #pragma unroll
     for (int s = 0; s < BK / 2; ++s) tile = mfma32x32x2(A[2 * s * H], B[2 * s * BN], tile);
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] += tile[r];
-#endif
     if (kt + 1 < nk) sstore(buf ^ 1);
     __syncthreads();
   }
@@ -299,9 +294,7 @@ __device__ inline void dw2_bf16_body(const bf16_t* __restrict__ X, int64_t ldx, 
 // factor per lane and 32-column half).  Each tile's run is found by a ballot over its 64
 // node_root entries (every wave computes the same run), so the next tile's start is known
 // when its loads are issued.  Layout, block ids and smem as dw2_bf16_body.
-#ifndef BGCN_DW2R_DEEP
-#define BGCN_DW2R_DEEP 1   // tiles whose loads are in flight (2: +20 VGPRs, two waves per SIMD: 4 % slower)
-#endif
+static_assert(kDw2bBK == 64, "a tile's run length comes from one 64-bit ballot");
 __device__ __forceinline__ float x_elem(const float* p) { return *p; }
 __device__ __forceinline__ float x_elem(const bf16_t* p) { return bf2f(*p); }
 template <class TX>
@@ -330,8 +323,8 @@ __device__ inline void dw2_root_body(const TX* __restrict__ X, int64_t ldx, int6
   const uint32_t wk = min(w0 + uint32_t(tid & 3), uint32_t(keep.nw - 1));
   const uint32_t voff_g = uint32_t(gn * (2 * H) + go) * 4u;     // this thread's first dZ2 element in a tile
   const float hsc = 0.5f * sc;                                  // exact: sc is 1 or 2
-  // one tile's loads in registers (BGCN_DW2R_DEEP 2 keeps two, issued two tiles before
-  // their LDS staging; the default relies on three waves per SIMD instead)
+  // one tile's loads in registers; three waves per SIMD hide the rest (tried two tiles'
+  // loads in flight: +20 VGPRs, two waves per SIMD, 4 % slower)
   struct Stage {
     float rg[kGN];
     uint32_t rk;
@@ -433,35 +426,6 @@ __device__ inline void dw2_root_body(const TX* __restrict__ X, int64_t ldx, int6
       for (int q = 0; q < 16; ++q) acc[ni][q] = fmaf(vv, tile[q], acc[ni][q]);
     }
   };
-#if BGCN_DW2R_DEEP == 2
-  // two tiles' loads in flight: the staged tile is multiplied while `nxt` holds the next
-  // tile's loads (start tn) and the one after is loaded into `fre`
-  auto step = [&](Stage& nxt, Stage& fre) -> bool {
-    const int64_t tnn = tn < ke ? tn + nxt.run : ke;
-    if (tnn < ke) gload(fre, tnn);
-    mul_tile();
-    __syncthreads();
-    if (tn >= ke) return false;   // block-uniform
-    sstore(nxt);
-    __syncthreads();
-    run = nxt.run;
-    v0 = nxt.vn[0]; v1 = nxt.vn[1];
-    tn = tnn;
-    return true;
-  };
-  Stage sa, sb;
-  if (kb < ke) {
-    gload(sa, kb);
-    sstore(sa);
-    run = sa.run;
-    v0 = sa.vn[0]; v1 = sa.vn[1];
-    tn = kb + run;
-    if (tn < ke) gload(sb, tn);
-    __syncthreads();
-    while (step(sb, sa) && step(sa, sb)) {
-    }
-  }
-#else
   // one tile's loads in flight (the occupancy hides the rest)
   Stage st;
   if (kb < ke) {
@@ -483,7 +447,6 @@ __device__ inline void dw2_root_body(const TX* __restrict__ X, int64_t ldx, int6
       tn += run;
     }
   }
-#endif
   float* out = cfg.part + (int64_t(d) * S + split) * (H * cfg.ldp) + H + n0;
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
@@ -603,40 +566,13 @@ __device__ inline void reduce_dw2_body(const float* __restrict__ part, int64_t K
 // from the operands the dH1 tile already holds: each lane's 16 (row, c) values of H1 and
 // of the keep words, in the accumulator row order acc_row(q, h), are its B fragments of
 // two 32x32x16 k-steps (element j of step s: row 16s + 8(j>>2) + 4h + (j&3)); the dZ2^T
-// fragments are read from the staged tile in that row order.  These products feed dW2
-// directly (no fan-in amplification: 2e-5 elementwise at every size), so they keep the
-// three-product split.  Two row-half waves are combined in LDS (fixed order).  One block
-// per node split (the tail reduces the splits).
+// fragments are read from the staged tile in that row order.  These products run in the
+// six-product form too (see the loop).  Two row-half waves are combined in LDS (fixed
+// order).  One block per node split (the tail reduces the splits).
 // Device body, 256 threads; smem: kDh1Smem floats.
-#ifndef BGCN_DH1_X6
-#define BGCN_DH1_X6 1   // 0: the three-product form (A/B only: not fp32-grade)
-#endif
-#ifndef BGCN_DW2P_X6
-#define BGCN_DW2P_X6 1   // the relu(H1) block of dW2 in the six-product form (0: three products)
-#endif
-#ifndef BGCN_DH1_PREFETCH
-#define BGCN_DH1_PREFETCH 1   // 0: the next tile's loads issued after the tile (A/B)
-#endif
 constexpr int kDh1Rows = 64;
 constexpr int kDsLd = H + 8;   // bf16 row stride of the staged, split tiles
 constexpr int kDh1Smem = (6 * kDh1Rows * kDsLd) / 2 + 2 * H;
-// dH1[i][d*H + c] = (dZ2_d[i] . W2_d[:, c]) * keep(d,i,c) * s * [H1 > 0], c < H,
-// + block partial column sums, over `rows` consecutive nodes (64-row tiles) of direction
-// d per block.  A 64-row x 64-column tile per 256-thread block, four waves as 2 row halves
-// x 2 column halves, on the bf16 MFMA in split form (mfma_x3, bgcn_common.h: this launch
-// was bound by the f32-input MFMA, 64 cycles per 32x32x2).  The dZ2 tile and W2[:, :64]^T
-// are staged in LDS already split (hi / lo bf16, rows of 72 = 16-byte aligned), so every
-// operand fragment of dH1 is one 16-byte LDS read.
-//
-// dw2part != nullptr (the sparse path, gated off when the dense path runs): the same
-// block also forms the relu(H1) block of dW2 over its rows,
-//   part[d][bx][o][c] = sum_i dZ2_d[i][o] * keep(d,i,c) * s * relu(H1_d[i][c]),
-// from the operands the dH1 tile already holds: each lane's 16 (row, c) values of H1 and
-// of the keep words, in the accumulator row order acc_row(q, h), are its B fragments of
-// two 32x32x16 k-steps (element j of step s: row 16s + 8(j>>2) + 4h + (j&3)); the dZ2^T
-// fragments are read from the staged tile in that row order.  Two row-half waves are
-// combined in LDS (fixed order).  One block per node split (the tail reduces the splits).
-// Device body, 256 threads; smem: kDh1Smem floats.
 __device__ inline void dh1_body(const float* __restrict__ dZ2, const float* __restrict__ H1,
                                 const float* __restrict__ W2td, const float* __restrict__ W2bu,
                                 int64_t ldw2, int64_t N, KeepSrc keep, float* __restrict__ dH1,
@@ -720,37 +656,25 @@ __device__ inline void dh1_body(const float* __restrict__ dZ2, const float* __re
     }
     // this tile's per-lane operands: a2 = keep * s * relu(H1) split (dW2's B fragments in
     // accumulator row order), bit q of km = kept and H1 > 0 (dH1)
-    bf16x8 a2h[2], a2l[2];
-#if BGCN_DW2P_X6
-    bf16x8 a2m[2];
-#endif
+    bf16x8 a2h[2], a2m[2], a2l[2];
     uint32_t km = 0;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       const int64_t i = row0 + (q & 3) + 8 * (q >> 2) + 4 * h;
       const uint32_t wd = keep.get(uint32_t(d), uint32_t(min<int64_t>(i, N - 1)), uint32_t(c >> 5));
       const bool kept = ((wd >> (c & 31)) & 1u) && i < N;
-#if BGCN_DW2P_X6
       __bf16 x, y, z;
       split3_bf16(kept ? sc * fmaxf(hv[q], 0.f) : 0.f, x, y, z);
       a2h[q >> 3][q & 7] = x;
       a2m[q >> 3][q & 7] = y;
       a2l[q >> 3][q & 7] = z;
-#else
-      __bf16 x, y;
-      split_bf16(kept ? sc * fmaxf(hv[q], 0.f) : 0.f, x, y);
-      a2h[q >> 3][q & 7] = x;
-      a2l[q >> 3][q & 7] = y;
-#endif
       km |= uint32_t(kept && hv[q] > 0.f) << q;
       if ((q & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // four keep hashes in flight
     }
     __syncthreads();
-#if BGCN_DH1_PREFETCH
     // the next tile's dZ2 rows and H1 values are in flight during this tile's products
     // (dv / hv are consumed above: staged in LDS, folded into km and a2)
     if (t + 1 < ntile) gload(blk0 + kDh1Rows);
-#endif
     // dH1: A = dZ2 rows (row rh*32 + r, o = 16s + 8h + j), B = W2^T (column c)
     f32x16 acc = {};
     const __bf16* ah = &Dh[(rh * 32 + r) * kDsLd + 8 * h];
@@ -761,16 +685,10 @@ __device__ inline void dh1_body(const float* __restrict__ dZ2, const float* __re
     const __bf16* bl = &Wl[c * kDsLd + 8 * h];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-#if BGCN_DH1_X6
       acc = mfma_x6(*reinterpret_cast<const bf16x8*>(ah + 16 * s), *reinterpret_cast<const bf16x8*>(am + 16 * s),
                     *reinterpret_cast<const bf16x8*>(al + 16 * s), *reinterpret_cast<const bf16x8*>(bh + 16 * s),
                     *reinterpret_cast<const bf16x8*>(bm + 16 * s), *reinterpret_cast<const bf16x8*>(bl + 16 * s),
                     acc);
-#else   // A/B: the three-product form (hi + mid = the two-way split)
-      (void)al; (void)bl;
-      acc = mfma_x3(*reinterpret_cast<const bf16x8*>(ah + 16 * s), *reinterpret_cast<const bf16x8*>(am + 16 * s),
-                    *reinterpret_cast<const bf16x8*>(bh + 16 * s), *reinterpret_cast<const bf16x8*>(bm + 16 * s), acc);
-#endif
       __builtin_amdgcn_sched_barrier(0);   // one k-step's fragments live at a time
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -787,7 +705,6 @@ __device__ inline void dh1_body(const float* __restrict__ dZ2, const float* __re
       // dW2: A = dZ2^T (o = r / 32 + r, rows in the a2 fragments' order), B = a2
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-#if BGCN_DW2P_X6
         // the fp32-grade six-product form (both operands split three ways, ~2^-24 relative):
         // the three-product form's ~1e-5 left the relu(H1) block of dW2 only 4-8x under
         // the 1e-4 bar at full size (profiles/r04_parity_*.json)
@@ -804,26 +721,10 @@ __device__ inline void dh1_body(const float* __restrict__ dZ2, const float* __re
         }
         pw0 = mfma_x6(z0h, z0m, z0l, a2h[s], a2m[s], a2l[s], pw0);
         pw1 = mfma_x6(z1h, z1m, z1l, a2h[s], a2m[s], a2l[s], pw1);
-#else
-        bf16x8 z0h, z0l, z1h, z1l;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int k = rh * 32 + 16 * s + 8 * (j >> 2) + 4 * h + (j & 3);
-          z0h[j] = Dh[k * kDsLd + r];
-          z0l[j] = Dm[k * kDsLd + r];
-          z1h[j] = Dh[k * kDsLd + 32 + r];
-          z1l[j] = Dm[k * kDsLd + 32 + r];
-        }
-        pw0 = mfma_x3(z0h, z0l, a2h[s], a2l[s], pw0);
-        pw1 = mfma_x3(z1h, z1l, a2h[s], a2l[s], pw1);
-#endif
         __builtin_amdgcn_sched_barrier(0);
       }
     }
     __syncthreads();   // the staged tile is rewritten by the next tile
-#if !BGCN_DH1_PREFETCH
-    if (t + 1 < ntile) gload(blk0 + kDh1Rows);
-#endif
   }
   cs += __shfl_xor(cs, 32);
   if (h == 0) red[rh][c] = cs;

@@ -156,25 +156,19 @@ __device__ __forceinline__ f32x16 mfma32x32x2(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
 
-// fp32 products on the bf16 MFMA.  The f32-input MFMA issues at the FP32 vector rate, 1/16
-// of the bf16 one; x = hi + lo with hi = bf16(x), lo = bf16(x - hi) keeps 16 of x's 24
-// mantissa bits, and a.b ~ ah.bh + ah.bl + al.bh (al.bl and the two residuals dropped,
-// each <= 2^-18 |a b|): ~1e-5 relative per product, accumulated in fp32.  Used where the
-// result feeds only linear steps (the backward's dH1 / dW2 products): a forward product
-// that feeds a relu flips its sign for entries near zero (measured on conv2: not used).
+// fp32 products on the bf16 MFMA: the f32-input MFMA issues at the FP32 vector rate, 1/16
+// of the bf16 one.
 // Lane map of 32x32x16: lane (h = l >> 5, r = l & 31) holds A[r][8h + j] and B[8h + j][r].
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
-__device__ __forceinline__ void split_bf16(float x, __bf16& hi, __bf16& lo) {
-  hi = __bf16(x);
-  lo = __bf16(x - float(hi));
-}
-// fp32-grade form (for products that feed a relu, where 1e-5 relative flips signs of
-// entries near zero): x = hi + mid + lo keeps all 24 bits, and a.b takes the six products
-// down to 2^-16 |a b| (al.bh, am.bm, ah.bl, am.bh, ah.bm, ah.bh, small terms first) - the
-// dropped ones are below 2^-24 |a b|, fp32's own rounding.
+// The fp32-grade form: x = hi + mid + lo (hi = bf16(x), mid = bf16(x - hi), ...) keeps all
+// 24 bits, and a.b takes the six products down to 2^-16 |a b| (al.bh, am.bm, ah.bl, am.bh,
+// ah.bm, ah.bh, small terms first) - the dropped ones are below 2^-24 |a b|, fp32's own
+// rounding.  (The two-way split x = hi + lo with three products is ~1e-5 relative per
+// product: in a forward product that feeds a relu it flips the sign of entries near zero,
+// and the backward's dH1 / dW2 products were not fp32-grade with it.)
 __device__ __forceinline__ void split3_bf16(float x, __bf16& hi, __bf16& mid, __bf16& lo) {
   hi = __bf16(x);
   const float r = x - float(hi);
@@ -190,15 +184,13 @@ __device__ __forceinline__ f32x16 mfma_x6(bf16x8 ah, bf16x8 am, bf16x8 al, bf16x
   c = mfma_bf16(ah, bm, c);
   return mfma_bf16(ah, bh, c);
 }
-// acc += a.b for split operands (three bf16 products, small terms first)
-__device__ __forceinline__ f32x16 mfma_x3(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f32x16 c) {
-  c = mfma_bf16(al, bh, c);
-  c = mfma_bf16(ah, bl, c);
-  return mfma_bf16(ah, bh, c);
-}
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+// a store of the chain's [N, 128] activations (Z1, H1, dZ2, dZ1, ...), which the next launch
+// alone reads (tried write-through (sc1) stores here: chain alone 148-151 vs 147-154 us, step
+// within noise)
+__device__ __forceinline__ void st4_chain(float* base, int64_t off, float4 v) { st4(base + off, v); }
 // streaming (non-temporal) 16-byte load: data read once, kept out of the caches' LRU
 __device__ __forceinline__ float4 ld4_nt(const float* p) {
   const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
@@ -267,23 +259,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void* row, uint
   void* base = reinterpret_cast<void*>(uint64_t(lo) | (uint64_t(hi) << 32));
   return __builtin_amdgcn_make_buffer_rsrc(base, 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
-__device__ __forceinline__ void st4_chain(float* base, int64_t off, float4 v) {
-#if BGCN_WT_OUT
-  u32x4 d;
-  d.x = __float_as_uint(v.x); d.y = __float_as_uint(v.y); d.z = __float_as_uint(v.z); d.w = __float_as_uint(v.w);
-  __builtin_amdgcn_raw_buffer_store_b128(d, row_rsrc(base, 0xfffffff0u), uint32_t(off * 4), 0, 16);   // sc1
-#else
-  st4(base + off, v);
-#endif
-}
-// The chain's [N, 128] activations (Z1, H1, dZ2, dZ1, ...) are read by the NEXT launch only:
-// stored write-through (sc1), the producer's kernel boundary has no dirty lines left to write
-// back (MI355X_MICROARCH.md price table, "boundary": + B / 6 TB/s for B dirty bytes, ~2.5 us
-// per 15 MB matrix).  base: wave-uniform; off: elements (32-bit byte offsets).
-#ifndef BGCN_WT_OUT
-#define BGCN_WT_OUT 0   // A/B r04: chain alone 148-151 vs 147-154 us, step within noise
-#endif
-__device__ __forceinline__ void st4_chain(float* base, int64_t off, float4 v);
 #ifndef BGCN_X_AUX
 #define BGCN_X_AUX 2   // A/B: the cache-policy bits of the pass over X (sc0 = 1, nt = 2, sc1 = 16)
 #endif

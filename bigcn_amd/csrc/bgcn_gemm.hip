@@ -264,7 +264,8 @@ __global__ __launch_bounds__(256) void k_gemm_tn(const float* __restrict__ G, in
 
 // The same partials with a 64 x 64 wave tile (block 128 x 128, four accumulators per
 // wave): one LDS operand read per f32 MFMA instead of 1.5, and a third less global
-// traffic per flop; 64 KB of LDS, two blocks per CU.  Vector-aligned operands only.
+// traffic per flop; 32 KB of LDS, four blocks per CU at the default k-tile depth of 16 (64 KB,
+// two blocks at 32).  Vector-aligned operands only.
 #ifndef BGCN_TN_WIDE_BK
 #define BGCN_TN_WIDE_BK 16   // k-tile depth (nodes; kchunk stays a multiple of BK = 32): 32 KB of LDS,
                              // four blocks per CU (32: 0.345 ms, 16: 0.322, 8: 0.327 at twitter15)

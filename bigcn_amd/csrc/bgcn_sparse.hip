@@ -535,82 +535,17 @@ __global__ __launch_bounds__(256) void k_compact_conv1(SparseState S, const TX* 
   compact_body<kConv1, TX>(S, X, ldx, Z1, int(blockIdx.x), int(gridDim.x));
 }
 
-// conv1 lin from a prepared ELL of X (bgcn_prepare_batch): four rows per wave, one per
-// 16-lane quarter, lane l of a quarter owning outputs [8l, 8l + 8) of the 128 (both
-// directions).  The kernel is latency-bound (ELL load -> W1^T row gathers from L2 ->
-// store per row), so a wave keeps four rows' gathers in flight instead of one
-// (measured at Weibo size: 62 us for one row per wave, beside nothing).  Entry s of a
-// row reaches its quarter by shuffle (entries s and s + 16 per lane); past a row's count
-// the value is 0 and the (clamped) column still loads, so every load is unconditional.
-constexpr int kC1Rows = 4;
-#ifndef BGCN_C1_THREADS
-#define BGCN_C1_THREADS 256
-#endif
-constexpr int kC1Threads = BGCN_C1_THREADS;   // threads per block
-__global__ __launch_bounds__(kC1Threads) void k_conv1_gather(SparseState S, float* __restrict__ Z1) {
-  BT_BEGIN
-  conv1_clears(S);
-  if (!use_sparse(S)) return;
-  const int lane = threadIdx.x & 63, ql = lane & 15, qb = lane & 48;
-  const int64_t i = (int64_t(blockIdx.x) * (kC1Threads / 64) + (threadIdx.x >> 6)) * kC1Rows + (lane >> 4);
-  const bool live = i < S.N;
-  const int64_t ic = live ? i : S.N - 1;
-  const int nall = live ? S.nnz[ic] : 0;
-  const int cnt = min(nall, kCap);
-  const int32_t c0 = S.cols[ic * kCap + ql], c1 = S.cols[ic * kCap + 16 + ql];
-  const float v0 = S.vals[ic * kCap + ql], v1 = S.vals[ic * kCap + 16 + ql];
-  // the wave's longest row bounds the loop (uniform)
-  int cmax = cnt;
-  cmax = max(cmax, __shfl_xor(cmax, 16, 64));
-  cmax = max(cmax, __shfl_xor(cmax, 32, 64));
-  float4 a0 = f4zero(), a1 = f4zero();
-  for (int s0 = 0; s0 < cmax; s0 += 8) {
-    float4 w0[8], w1[8];
-    float x[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int sl = s0 + u;                          // uniform
-      const int src = qb + (sl & 15);
-      const int32_t c = __shfl(sl < 16 ? c0 : c1, src, 64);
-      const float v = __shfl(sl < 16 ? v0 : v1, src, 64);
-      x[u] = sl < cnt ? v : 0.f;
-      const int32_t cc = min(max(c, 0), int32_t(S.F - 1));
-      const float* wr = S.w1t + int64_t(cc) * (2 * H) + 8 * ql;
-      w0[u] = ld4(wr);
-      w1[u] = ld4(wr + 4);
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      a0 = f4fma(x[u], w0[u], a0);
-      a1 = f4fma(x[u], w1[u], a1);
-    }
-  }
-  if (nall > kCap) {   // spilled entries of a long row (rare): one at a time
-    const int64_t off = S.ovf_off[ic];
-    for (int k = 0; k < nall - kCap; ++k) {
-      const uint2 e = S.ovf[off + k];
-      const float v = __uint_as_float(e.y);
-      const float* wr = S.w1t + int64_t(min(max(int32_t(e.x), 0), int32_t(S.F - 1))) * (2 * H) + 8 * ql;
-      a0 = f4fma(v, ld4(wr), a0);
-      a1 = f4fma(v, ld4(wr + 4), a1);
-    }
-  }
-  if (live) {
-    st4_chain(Z1, i * (2 * H) + 8 * ql, a0);
-    st4_chain(Z1, i * (2 * H) + 8 * ql + 4, a1);
-  }
-  BT_END(1);
-}
-
-// The same product with two rows per wave: half-wave h (32 lanes) owns row 2w + h, lane
-// l of a half the outputs [4l, 4l + 4) - one 16-byte load per lane per entry, a wave
-// instruction still moves 1 KiB (two 512-byte W1^T rows).  The loop runs to the longer
-// of the two rows in steps of kStep entries (a wave-uniform bound), so a wave issues
-// fewer padded gathers than with four rows, and holds fewer registers (more waves per
-// SIMD).
-#ifndef BGCN_C1_MODE
-#define BGCN_C1_MODE 2   // 0: four rows per wave (k_conv1_gather); 1 / 2: two rows, steps of 8 / 4
-#endif
+// conv1 lin from a prepared ELL of X (bgcn_prepare_batch), the 128 outputs of both
+// directions per row.  The kernel is latency-bound (ELL load -> W1^T row gathers from L2 ->
+// store per row), so a wave keeps several rows' gathers in flight instead of one (measured
+// at Weibo size: 62 us for one row per wave, beside nothing).  Two rows per wave: half-wave
+// h (32 lanes) owns row 2w + h, lane l of a half the outputs [4l, 4l + 4) - one 16-byte load
+// per lane per entry, a wave instruction still moves 1 KiB (two 512-byte W1^T rows).  Entry
+// s of a row reaches its half by shuffle; past a row's count the value is 0 and the
+// (clamped) column still loads, so every load is unconditional.  The loop runs to the
+// longer of the two rows in steps of kStep entries (a wave-uniform bound; 4 is the one
+// instantiation).  Tried four rows per wave (one per 16-lane quarter, steps of 8) and two
+// rows in steps of 8: more padded gathers and more registers (fewer waves per SIMD).
 // Long rows (more than kCap non-zeros: the ELL list + the spill pool) get a block each
 // instead of a half-wave: a long row walked by one half-wave is a serial chain of gathers
 // (270 entries: ~70 us at 4 in flight), so the block's four waves take a quarter of the
@@ -672,58 +607,13 @@ __device__ __forceinline__ float4 conv1_half_entries(const SparseState& S, int32
   }
   return acc;
 }
-// conv2's root-slot B operand of tree b, direction d (SparseState::rimg): slot s of the
-// root's ELL list holds 2 relu(x_root,col_s) W2_d^T[64 + col_s] at k = (s & 1) 16 + (s >> 1)
-// of the image's 32-wide rows, split hi / mid / lo - the operand conv2's fill built per item
-// from three dependent loads (item root -> its ELL slots -> W2^T rows); one block per (tree,
-// direction) of conv1's launch, where the chain has the loads' latency to spare.
-__device__ inline void root_image_block(const SparseState& S, const int64_t* __restrict__ rootindex, float sc,
-                                        int blk) {
-  const int b = blk >> 1, d = blk & 1;
-  const int64_t r0 = rootindex[b];
-  const int64_t r = r0 >= 0 && r0 < S.N ? r0 : 0;   // (a bad root id is flagged by the batch checks)
-  const int rn_all = S.nnz[r];
-  const int rn = min(rn_all, kCap);
-  const float* w2t = S.w2t + int64_t(d) * (S.F + H) * H;
-  __bf16* img = S.rimg + (int64_t(b) * 2 + d) * 3 * H * kCap;
-  if (d == 0 && threadIdx.x < kCap)
-    S.rcols[int64_t(b) * kCap + threadIdx.x] = threadIdx.x < rn ? uint32_t(H + S.cols[r * kCap + threadIdx.x]) : 0u;
-  if (d == 0 && threadIdx.x == 0) S.rinfo[b] = rn_all;
-  for (int e = threadIdx.x; e < kCap * (H / 4); e += int(blockDim.x)) {
-    const int s = e >> 4, q = (e & 15) * 4;
-    const int64_t slot = r * kCap + s;
-    const int32_t col = min(max(S.cols[slot], 0), int32_t(S.F - 1));
-    const float val = S.vals[slot];
-    const float4 w = ld4(w2t + int64_t(H + col) * H + q);
-    const float av = s < rn ? sc * fmaxf(val, 0.f) : 0.f;
-    const float vv[4] = {av * w.x, av * w.y, av * w.z, av * w.w};
-    const int k = (s & 1) * (kCap / 2) + (s >> 1);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      __bf16 x, y, z;
-      split3_bf16(vv[u], x, y, z);
-      const int64_t o = int64_t(q + u) * kCap + k;
-      img[o] = x;
-      img[H * kCap + o] = y;
-      img[2 * H * kCap + o] = z;
-    }
-  }
-}
-
-// Blocks [0, nroot): conv2's root images (root_image_block, 2 per tree when the caller wants
-// them, else none); then [nroot, nroot + kLongRowBlocks): the long rows (conv1_long_rows);
-// then two rows per wave.
+// Blocks [0, kLongRowBlocks): the long rows (conv1_long_rows); then two rows per wave.
 template <int kStep>
-__global__ __launch_bounds__(256) void k_conv1_rows2(SparseState S, float* __restrict__ Z1,
-                                                     const int64_t* __restrict__ rootindex, float sc, int nroot) {
+__global__ __launch_bounds__(256) void k_conv1_rows2(SparseState S, float* __restrict__ Z1) {
   BT_BEGIN
   conv1_clears(S);
   if (!use_sparse(S)) return;
-  if (int(blockIdx.x) < nroot) {
-    root_image_block(S, rootindex, sc, int(blockIdx.x));
-    return;
-  }
-  const int bx = int(blockIdx.x) - nroot;
+  const int bx = int(blockIdx.x);
   if (bx < kLongRowBlocks) {
     conv1_long_rows(S, Z1, bx, kLongRowBlocks);
     return;
@@ -744,13 +634,13 @@ __global__ __launch_bounds__(256) void k_conv1_rows2(SparseState S, float* __res
 }
 
 // ---------------------------------------------------------------- conv2 forward
-// conv2 lin on the sparse path, one work item (<= kChunk nodes of one tree) per block:
+// conv2 lin on the sparse path, per work item (<= kChunk nodes of one tree):
 //   Z2_d[i] = [keep * 2 relu(H1_d[i]) | kept_d(i, s)] . [W2_d^T[0:64] ; Wr_b]
 //   Wr_b[s] = 2 relu(x_root,col_s) W2_d^T[64 + col_s]      (s < nnz(root), else 0)
 // i.e. one [nodes x (64 + nnz(root))] x [. x 64] product per item, with the dropout-masked
 // relu(H1) and the per-node root keep bits (0/1) generated in registers and the block's B
 // operand staged once in LDS.  The root keep masks are stored in S.rbits for the dW2 root
-// columns of the backward.  Each wave stages its 32-row H1 tile through LDS (coalesced).
+// columns of the backward.
 //
 // The product runs on the bf16 MFMA in the fp32-grade split form (mfma_x6, bgcn_common.h):
 // the f32-input MFMA issues at the FP32 vector rate and bounds this kernel at Weibo /
@@ -761,303 +651,23 @@ __global__ __launch_bounds__(256) void k_conv1_rows2(SparseState S, float* __res
 // columns [32h, 32h + 32) (k-step s: columns 32h + 8s + j) and root slots 2j + h (k-step
 // t: slots 2(8t + j) + h), so each lane hashes only its own keep words and the steps past
 // the root's non-zeros are skipped; the keep bits are exact in bf16 (three products).
-#ifndef BGCN_C2_PREFETCH
-#define BGCN_C2_PREFETCH 1   // 0: each H1 tile requested when it is staged (30 VGPRs fewer)
-#endif
-constexpr int kC2Ld = H + 1;             // f32 row stride of the staged H1 tiles
+//
+// Every wave works on ONE 32-node tile: a block takes half a work item (tiles 4 half ..
+// 4 half + 3; the second half of an item of <= 128 nodes exits at once), so no wave runs two
+// tiles in series, and each lane loads its H1 A-fragment (row r32, columns [32h, 32h + 32)
+// of direction d: eight 16-byte loads, a 128-byte run) straight into registers at the
+// kernel's start, under the B fill - no LDS staging of H1 (the block's LDS is the B operand
+// only).  Tried a block per whole item (two tiles per wave in series, H1 staged through
+// LDS): the kernel was the fill plus two tiles' products on the items of 256 nodes.
+// Tried per-tree root images built by extra blocks of conv1's launch (one dependent level
+// less in this fill): conv1 alone 15.6 -> 19.5 us for its 2B extra blocks, conv2 unchanged
+// (20.6 -> 20.2), the step not faster (profiles/r05_pass_regs_ab.txt and the round-5
+// root-image timelines beside it).
 constexpr int kC2K = H + kCap;           // B rows: 64 H1 columns + 32 root slot positions
 constexpr int kC2Ld16 = kC2K + 8;        // bf16 row stride of the split B (16-byte aligned)
-__global__ __launch_bounds__(256) void k_conv2_sparse(SparseState S, const float* __restrict__ H1,
-                                                      const int32_t* __restrict__ tree_ptr,
-                                                      const int64_t* __restrict__ rootindex,
-                                                      float* __restrict__ Z2, KeepSrc keep) {
-  BT_BEGIN
-  if (!use_sparse(S)) return;
-  const int item = blockIdx.x;
-  if (item >= S.tree_item0[S.B]) return;
-  __shared__ __attribute__((aligned(16))) __bf16 Bs[3][H * kC2Ld16];   // hi, mid, lo
-  __shared__ float Hs[4 * 32 * kC2Ld];
-  __shared__ uint32_t rk[kCap];
-  const int d = blockIdx.y;
-  const int64_t beg = S.item_beg[item], end = S.item_end[item];
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, r32 = l & 31, h = l >> 5;
-  // the wave's first H1 tile is requested before the B fill's dependent chain (root ->
-  // its ELL slots -> W2^T rows) starts, so its latency hides behind the fill; a tile past
-  // the item loads (clamped) rows it then ignores - no load under a branch
-  auto h1load = [&](int t, float4 (&hv)[8]) {   // coalesced: 8 x 1 KiB per wave
-    const int64_t i0 = beg + 32 * t;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int e = l + 64 * u, rr = e >> 4, q = (e & 15) * 4;
-      hv[u] = ld4(H1 + min<int64_t>(i0 + rr, end - 1) * (2 * H) + d * H + q);
-    }
-  };
-  float4 hv[8];
-  if (BGCN_C2_PREFETCH) h1load(wv, hv);
-  const int64_t r = S.item_root[item];
-  const int rn_all = S.nnz[r];
-  const int rn = min(rn_all, kCap);   // root slots in the ELL (the rest spilled)
-  const int mh = (rn + 1) / 2;   // root slot pairs (slot 2j + h, j < mh)
-  const float sc = keep.scale();
-  const int64_t K2 = S.F + H;
-  const float* w2t = S.w2t + int64_t(d) * K2 * H;
-  // B fill with unconditional loads (clamped slot / column; see k_dh1), selects after
-  if (threadIdx.x < kCap)
-    rk[threadIdx.x] = threadIdx.x < rn ? uint32_t(H + S.cols[r * kCap + threadIdx.x]) : 0u;
-  {   // k < 64: the prologue's split image of W2_d[:, :64] (16-byte copies, 8 per row part)
-    static_assert(kC2Ld16 == kW2sLd, "conv2's B rows are the prologue image's rows");
-    const __bf16* src = S.w2s + int64_t(d) * 3 * H * kW2sLd;
-    for (int e = threadIdx.x; e < 3 * H * 8; e += 256) {
-      const int part = e / (H * 8), o = (e / 8) % H, q = (e % 8) * 8;
-      *reinterpret_cast<uint4*>(&Bs[part][o * kC2Ld16 + q]) =
-          *reinterpret_cast<const uint4*>(src + (int64_t(part) * H + o) * kW2sLd + q);
-    }
-  }
-  for (int e = threadIdx.x; e < kCap * (H / 4); e += 256) {  // root slots (zero past rn)
-    const int s = e >> 4, q = (e & 15) * 4;
-    const int64_t slot = r * kCap + s;              // always inside the row's ELL list
-    const int32_t col = min(max(S.cols[slot], 0), int32_t(S.F - 1));
-    const float val = S.vals[slot];
-    const float4 w = ld4(w2t + int64_t(H + col) * H + q);
-    const float av = s < rn ? sc * fmaxf(val, 0.f) : 0.f;
-    const float vv[4] = {av * w.x, av * w.y, av * w.z, av * w.w};
-    const int k = H + (s & 1) * (kCap / 2) + (s >> 1);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int o = (q + u) * kC2Ld16 + k;
-      split3_bf16(vv[u], Bs[0][o], Bs[1][o], Bs[2][o]);
-    }
-  }
-  __syncthreads();
-  BT_MARK(2, 0);
-
-  float* hs = &Hs[wv * 32 * kC2Ld];   // this wave's staged 32 x 64 H1 tile
-  auto h1stage = [&](const float4 (&hv)[8]) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int e = l + 64 * u, rr = e >> 4, q = (e & 15) * 4;
-      float* dst = &hs[rr * kC2Ld + q];
-      dst[0] = hv[u].x; dst[1] = hv[u].y; dst[2] = hv[u].z; dst[3] = hv[u].w;
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS writes landed
-    __builtin_amdgcn_wave_barrier();
-  };
-  // the main product of tile t (32 nodes of the item): H1 tile staged through LDS, the
-  // dropout-masked relu(H1) and the root keep bits generated in registers, six-product
-  // bf16 MFMAs; the root keep masks go to S.rbits
-  // (the tile's H1 rows are in the wave's LDS tile already: h1stage)
-  auto tile = [&](int t, f32x16& acc0, f32x16& acc1) {
-    const int64_t i0 = beg + 32 * t;
-    const int64_t i = i0 + r32;
-    const bool ok = i < end;
-    if (t == wv) BT_MARK(2, 1);
-    const float* hrow = &hs[r32 * kC2Ld + 32 * h];
-    const uint32_t ni = uint32_t(ok ? i : beg);
-    const uint32_t kb = keep.base(ni);   // the node's hash base, shared by its words
-    const uint32_t wd = keep.get_b(uint32_t(d), ni, kb, uint32_t(h));
-    uint32_t m = 0;
-#pragma unroll
-    for (int j = 0; j < kCap / 2; ++j) {
-      uint32_t bit = 0;
-      if (j < mh) {
-        const int sl = 2 * j + h;
-        const uint32_t k = rk[sl];
-        bit = sl < rn ? (keep.get_b(uint32_t(d), ni, kb, k >> 5) >> (k & 31)) & 1u : 0u;
-      }
-      m |= bit << (2 * j + h);
-    }
-    acc0 = f32x16{};
-    acc1 = f32x16{};
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {   // H1 columns 32h + 8s + j
-      bf16x8 ah, am, al;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int kk = 8 * s + j;
-        const float a = ((wd >> kk) & 1u) ? sc * fmaxf(hrow[kk], 0.f) : 0.f;
-        __bf16 x, y, z;
-        split3_bf16(a, x, y, z);
-        ah[j] = x; am[j] = y; al[j] = z;
-      }
-      const int k = 32 * h + 8 * s;
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const int o = (32 * half + r32) * kC2Ld16 + k;
-        const bf16x8 bh = *reinterpret_cast<const bf16x8*>(&Bs[0][o]);
-        const bf16x8 bm = *reinterpret_cast<const bf16x8*>(&Bs[1][o]);
-        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(&Bs[2][o]);
-        if (half == 0) acc0 = mfma_x6(ah, am, al, bh, bm, bl, acc0);
-        else acc1 = mfma_x6(ah, am, al, bh, bm, bl, acc1);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {   // root slots 2(8tt + j) + h
-      if (8 * tt < mh) {
-        bf16x8 ar;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ar[j] = __bf16(((m >> (2 * (8 * tt + j) + h)) & 1u) ? 1.f : 0.f);
-        const int k = H + (kCap / 2) * h + 8 * tt;
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-          const int o = (32 * half + r32) * kC2Ld16 + k;
-          f32x16 c = half == 0 ? acc0 : acc1;
-          c = mfma_bf16(ar, *reinterpret_cast<const bf16x8*>(&Bs[2][o]), c);
-          c = mfma_bf16(ar, *reinterpret_cast<const bf16x8*>(&Bs[1][o]), c);
-          c = mfma_bf16(ar, *reinterpret_cast<const bf16x8*>(&Bs[0][o]), c);
-          if (half == 0) acc0 = c; else acc1 = c;
-        }
-      }
-    }
-    m |= __shfl_xor(m, 32);
-    if (h == 0 && ok) S.rbits[int64_t(d) * S.N + i] = m;
-    if (t == wv) BT_MARK(2, 2);
-  };
-  auto store = [&](int t, const f32x16& acc0, const f32x16& acc1) {
-    const int64_t i0 = beg + 32 * t;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int64_t ii = i0 + (q & 3) + 8 * (q >> 2) + 4 * h;
-      if (ii < end) {
-        Z2[ii * (2 * H) + d * H + r32] = acc0[q];
-        Z2[ii * (2 * H) + d * H + 32 + r32] = acc1[q];
-      }
-    }
-  };
-  static_assert(kChunk / 32 == 8, "two tiles per wave");
-  if (rn_all <= kCap) {
-    // tile wv (its H1 rows requested at the start), then tile wv + 4, whose rows are
-    // requested as soon as the first tile's are staged: in flight during its products
-    if (beg + 32 * wv < end) {
-      if (!BGCN_C2_PREFETCH) h1load(wv, hv);
-      h1stage(hv);
-      if (BGCN_C2_PREFETCH) h1load(wv + 4, hv);
-      f32x16 acc0, acc1;
-      tile(wv, acc0, acc1);
-      store(wv, acc0, acc1);
-      if (beg + 32 * (wv + 4) < end) {
-        if (!BGCN_C2_PREFETCH) h1load(wv + 4, hv);
-        h1stage(hv);
-        tile(wv + 4, acc0, acc1);
-        store(wv + 4, acc0, acc1);
-      }
-    }
-  } else {
-    // The root's spilled non-zeros (a root row of more than kCap words, rare): further
-    // [nodes x 32] x [32 x 64] products of the same form as the root slots - A the exact
-    // 0/1 keep bits, B = 2 relu(x_root,c) W2_d^T[64 + c] split three ways - 32 pool entries
-    // per round, accumulated into the wave's two tiles held in registers (no Z2 round
-    // trips), then stored.  Software-pipelined: the pool entries are loaded two rounds
-    // ahead and the W2^T rows they select one round ahead, so a round's dependent loads
-    // hide behind the previous round's products.
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      if (beg + 32 * (wv + 4 * j) < end) {
-        if (j == 1 || !BGCN_C2_PREFETCH) h1load(wv + 4 * j, hv);
-        h1stage(hv);
-        tile(wv + 4 * j, acc[j][0], acc[j][1]);
-      }
-    const int64_t off = S.ovf_off[r];
-    const int nsp = rn_all - kCap;
-    const int sq0 = threadIdx.x >> 4, sq1 = (threadIdx.x + 256) >> 4, qq = (threadIdx.x & 15) * 4;
-    auto ent_at = [&](int c0, int s_) { return S.ovf[off + min(c0 + s_, nsp - 1)]; };
-    auto w_of = [&](uint2 e) {
-      return ld4(w2t + int64_t(H + min(max(int32_t(e.x), 0), int32_t(S.F - 1))) * H + qq);
-    };
-    const int tk = min(int(threadIdx.x), kCap - 1);
-    uint2 e0 = ent_at(0, sq0), e1 = ent_at(0, sq1), rkc = ent_at(0, tk);
-    uint2 n0 = ent_at(kCap, sq0), n1 = ent_at(kCap, sq1), rkn = ent_at(kCap, tk);
-    float4 w0 = w_of(e0), w1 = w_of(e1);
-    for (int c0 = 0; c0 < nsp; c0 += kCap) {
-      const int cn = min(kCap, nsp - c0);
-      __syncthreads();   // every wave is done with Bs / rk
-      if (threadIdx.x < kCap) rk[threadIdx.x] = uint32_t(H + min(max(int32_t(rkc.x), 0), int32_t(S.F - 1)));
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int s_ = j == 0 ? sq0 : sq1;
-        const uint2 ent = j == 0 ? e0 : e1;
-        const float4 w = j == 0 ? w0 : w1;
-        const float av = s_ < cn ? sc * fmaxf(__uint_as_float(ent.y), 0.f) : 0.f;
-        const float vv[4] = {av * w.x, av * w.y, av * w.z, av * w.w};
-        const int k = H + (s_ & 1) * (kCap / 2) + (s_ >> 1);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int o = (qq + u) * kC2Ld16 + k;
-          split3_bf16(vv[u], Bs[0][o], Bs[1][o], Bs[2][o]);
-        }
-      }
-      __syncthreads();
-      // the next rounds' loads, in flight during this round's products
-      e0 = n0; e1 = n1; rkc = rkn;
-      n0 = ent_at(c0 + 2 * kCap, sq0); n1 = ent_at(c0 + 2 * kCap, sq1); rkn = ent_at(c0 + 2 * kCap, tk);
-      w0 = w_of(e0); w1 = w_of(e1);
-      const int mc = (cn + 1) / 2;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int64_t i0 = beg + 32 * (wv + 4 * j);
-        if (i0 >= end) continue;
-        const int64_t i = i0 + r32;
-        const uint32_t ni = uint32_t(i < end ? i : beg);
-        const uint32_t kb = keep.base(ni);
-        uint32_t m = 0;
-#pragma unroll
-        for (int jj = 0; jj < kCap / 2; ++jj) {
-          const int sl = 2 * jj + h;
-          if (jj < mc && sl < cn) {
-            const uint32_t k = rk[sl];
-            m |= ((keep.get_b(uint32_t(d), ni, kb, k >> 5) >> (k & 31)) & 1u) << sl;
-          }
-        }
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-          if (8 * tt < mc) {
-            bf16x8 ar;
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) ar[jj] = __bf16(((m >> (2 * (8 * tt + jj) + h)) & 1u) ? 1.f : 0.f);
-            const int k = H + (kCap / 2) * h + 8 * tt;
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-              const int o = (32 * half + r32) * kC2Ld16 + k;
-              f32x16 c = acc[j][half];
-              c = mfma_bf16(ar, *reinterpret_cast<const bf16x8*>(&Bs[2][o]), c);
-              c = mfma_bf16(ar, *reinterpret_cast<const bf16x8*>(&Bs[1][o]), c);
-              acc[j][half] = mfma_bf16(ar, *reinterpret_cast<const bf16x8*>(&Bs[0][o]), c);
-            }
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      if (beg + 32 * (wv + 4 * j) < end) store(wv + 4 * j, acc[j][0], acc[j][1]);
-  }
-  BT_END(2);
-}
-
-
-// The same conv2 with every wave on ONE 32-node tile: a block takes half a work item
-// (tiles 4 half .. 4 half + 3; the second half of an item of <= 128 nodes exits at once), so
-// no wave runs two tiles in series (the whole kernel was the fill plus two tiles' products
-// on the items of 256 nodes), and each lane loads its H1 A-fragment (row r32, columns
-// [32h, 32h + 32) of direction d: eight 16-byte loads, a 128-byte run) straight into
-// registers at the kernel's start, under the B fill - no LDS staging of H1 (the block's LDS
-// is the B operand only).  BGCN_C2_HALF=0 keeps k_conv2_sparse.
-#ifndef BGCN_C2_HALF
-#define BGCN_C2_HALF 1
-#endif
-// 1: conv2_half copies per-tree root images that extra blocks of conv1's launch build (one
-// dependent level less in conv2's fill).  Measured (profiles/r05_pass_regs_ab.txt,
-// r05_timeline_*_rimg.txt): conv1 alone 15.6 -> 19.5 us for its 2B extra blocks, conv2
-// unchanged (20.6 -> 20.2), the step not faster - off.
+static_assert(kC2Ld16 == kW2sLd, "conv2's B rows are the prologue image's rows");
 #ifndef BGCN_C2H_WAVES
 #define BGCN_C2H_WAVES 1   // min waves per SIMD (register budget: 5 -> <= 96, beside two waves of the pass)
-#endif
-#ifndef BGCN_C2H_PREFETCH
-#define BGCN_C2H_PREFETCH 1
-#endif
-#ifndef BGCN_C2_RIMG
-#define BGCN_C2_RIMG 0
 #endif
 __global__ __launch_bounds__(256, BGCN_C2H_WAVES) void k_conv2_half(SparseState S, const float* __restrict__ H1,
                                                     float* __restrict__ Z2, KeepSrc keep) {
@@ -1077,15 +687,12 @@ __global__ __launch_bounds__(256, BGCN_C2H_WAVES) void k_conv2_half(SparseState 
   const bool ok = i < end;
   const bool live = i0 < end;                        // wave-uniform: the wave has a tile
   // this lane's A-fragment rows (clamped: a row past the item reads the item's last row and
-  // is masked by `ok`), requested before the fill (BGCN_C2H_PREFETCH) or after it - the
-  // latter keeps the 32 registers free during the fill: 114 -> ~84 per wave, so the kernel
-  // fits beside two waves of the pass over X (2 x 208 + 96 <= 512) on every CU
+  // is masked by `ok`), requested before the fill.  (Requested after it, the 32 registers
+  // stay free during the fill, 114 -> ~84 per wave - tried, not kept.)
   float4 hv[8];
   const float* hsrc = H1 + min<int64_t>(i, end - 1) * (2 * H) + d * H + 32 * h;
-  if (BGCN_C2H_PREFETCH) {
 #pragma unroll
-    for (int u = 0; u < 8; ++u) hv[u] = ld4(hsrc + 4 * u);
-  }
+  for (int u = 0; u < 8; ++u) hv[u] = ld4(hsrc + 4 * u);
   const int64_t r = S.item_root[item];
   const float sc = keep.scale();
   const int64_t K2 = S.F + H;
@@ -1098,26 +705,12 @@ __global__ __launch_bounds__(256, BGCN_C2H_WAVES) void k_conv2_half(SparseState 
           *reinterpret_cast<const uint4*>(src + (int64_t(part) * H + o) * kW2sLd + q);
     }
   }
-  int rn_all;
-  if (S.rimg_ready) {   // the tree's root image from conv1's launch: one dependent level
-    const int b = S.item_tree[item];
-    rn_all = S.rinfo[b];
-    if (threadIdx.x < kCap) rk[threadIdx.x] = S.rcols[int64_t(b) * kCap + threadIdx.x];
-    const __bf16* img = S.rimg + (int64_t(b) * 2 + d) * 3 * H * kCap;
-    for (int e = threadIdx.x; e < 3 * H * (kCap / 8); e += 256) {   // 16-byte pieces: 4 per 32-wide row
-      const int part = e / (H * 4), o = (e / 4) % H, q = (e % 4) * 8;
-      *reinterpret_cast<uint4*>(&Bs[part][o * kC2Ld16 + H + q]) =
-          *reinterpret_cast<const uint4*>(img + (int64_t(part) * H + o) * kCap + q);
-    }
-  } else {
-    rn_all = S.nnz[r];
-  }
-  const int rn = min(rn_all, kCap);
-  const int mh = (rn + 1) / 2;
-  (void)mh;
-  if (!S.rimg_ready && threadIdx.x < kCap)
+  const int rn_all = S.nnz[r];
+  const int rn = min(rn_all, kCap);   // root slots in the ELL (the rest spilled)
+  // the root slots, with unconditional loads (clamped slot / column), selects after
+  if (threadIdx.x < kCap)
     rk[threadIdx.x] = threadIdx.x < rn ? uint32_t(H + S.cols[r * kCap + threadIdx.x]) : 0u;
-  for (int e = threadIdx.x; !S.rimg_ready && e < kCap * (H / 4); e += 256) {
+  for (int e = threadIdx.x; e < kCap * (H / 4); e += 256) {   // (zero past rn)
     const int s = e >> 4, q = (e & 15) * 4;
     const int64_t slot = r * kCap + s;
     const int32_t col = min(max(S.cols[slot], 0), int32_t(S.F - 1));
@@ -1134,10 +727,6 @@ __global__ __launch_bounds__(256, BGCN_C2H_WAVES) void k_conv2_half(SparseState 
   }
   __syncthreads();
   BT_MARK(2, 0);
-  if (!BGCN_C2H_PREFETCH) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) hv[u] = ld4(hsrc + 4 * u);
-  }
   // a wave without a tile (the half's last tiles past a short item) computes nothing but
   // stays for the spill rounds' barriers
   const uint32_t ni = uint32_t(ok ? i : beg);
@@ -1896,10 +1485,6 @@ constexpr int kSliceW = 2 * H / kSlices;          // outputs per slice
 constexpr int kSliceLanes = kSliceW / 4;          // lanes per entry (one float4 each)
 constexpr int kSliceGroups = 64 / kSliceLanes;    // entries per gather instruction
 constexpr int kSliceDepth = BGCN_DW1_DEPTH;
-#ifndef BGCN_DW1_CSC_PF
-#define BGCN_DW1_CSC_PF 1
-#endif
-constexpr bool kDw1CscPf = BGCN_DW1_CSC_PF != 0;
 static_assert(8 % kSlices == 0 && kSliceW <= H && kSliceLanes >= 1, "slices");
 __device__ __forceinline__ float4 shfl4(float4 v, int src) {
   return make_float4(__shfl(v.x, src, 64), __shfl(v.y, src, 64), __shfl(v.z, src, 64), __shfl(v.w, src, 64));
@@ -1953,20 +1538,15 @@ __device__ inline void dw1_sliced_body(const SparseState& S, const float* __rest
   bool spill_root = false;
   if (c < F) {
     const int64_t beg = S.col_start[c], end = S.col_end[c];
-    // the next 64 CSC entries are requested before this chunk's gathers (BGCN_DW1_CSC_PF):
+    // the next 64 CSC entries are requested before this chunk's gathers (clamped: duplicates, x masked):
     // loads retire in order, so they cost no wait, and the chunk loop then takes one
     // dependent round trip less per 64 entries
     // (32-bit entry indices: the CSC holds fewer than 2^31 entries, kSparseMaxN)
     const int32_t be = int32_t(beg), en = int32_t(end);
     uint2 ent_nx = be < en ? S.csc[min(be + lane, en - 1)] : make_uint2(0u, 0u);
     for (int32_t u0 = be; u0 < en; u0 += 64) {
-      uint2 ent;
-      if constexpr (kDw1CscPf) {
-        ent = ent_nx;
-        if (u0 + 64 < en) ent_nx = S.csc[min(u0 + 64 + lane, en - 1)];
-      } else {
-        ent = S.csc[min(u0 + lane, en - 1)];   // clamped: duplicates, x masked
-      }
+      const uint2 ent = ent_nx;
+      if (u0 + 64 < en) ent_nx = S.csc[min(u0 + 64 + lane, en - 1)];
       const uint32_t slot = ent.x & kCscSlotMask;
       const int n = min(64, en - u0);
       const float x_l = lane < n ? __uint_as_float(ent.y) : 0.f;
@@ -2419,7 +1999,7 @@ __global__ __launch_bounds__(256) void k_dw2_bf16(BwdMidArgs a) {
 // applied per tile in fp32), same LDS and block ids; TX = bf16_t: the same form for bf16 X
 // (the default; BGCN_DW2_ROOT=0 keeps k_dw2_bf16).
 #ifndef BGCN_DW2R_WPE
-#define BGCN_DW2R_WPE 3   // three waves per SIMD (162 VGPRs at BGCN_DW2R_DEEP 1)
+#define BGCN_DW2R_WPE 3   // three waves per SIMD (dw2_root_body: 162 VGPRs)
 #endif
 template <class TX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BGCN_DW2R_WPE))) void k_dw2_root(BwdMidArgs a) {
@@ -2539,10 +2119,9 @@ size_t carve_sparse(Carve& c, int64_t N, int64_t B, int64_t F, SparseState* S) {
   t.F = F;
   t.B = B;
   t.max_items = int(N / kChunk + B + 1);
-  t.w1t = c.take<float>(size_t(F) * 2 * H);
-  t.w2t = c.take<float>(size_t(2) * (F + H) * H);
-  t.w2s = c.take<__bf16>(size_t(2) * 3 * H * kW2sLd);
-  t.w2d = c.take<__bf16>(size_t(2) * 3 * H * kW2dLd);
+  WeightImages im;
+  carve_images(c, F, &im);
+  t.w1t = im.w1t; t.w2t = im.w2t; t.w2s = im.w2s; t.w2d = im.w2d;
   t.item_tree = c.take<int32_t>(size_t(t.max_items));
   t.item_beg = c.take<int32_t>(size_t(t.max_items));
   t.item_end = c.take<int32_t>(size_t(t.max_items));
@@ -2561,9 +2140,6 @@ size_t carve_sparse(Carve& c, int64_t N, int64_t B, int64_t F, SparseState* S) {
   t.ovf_cap = N * kSpillPerRow;             // batch brings its own)
   t.ovf = c.take<uint2>(size_t(t.ovf_cap));
   t.long_rows = c.take<int32_t>(size_t(N));
-  t.rimg = c.take<__bf16>(size_t(B) * 2 * 3 * H * kCap);
-  t.rcols = c.take<uint32_t>(size_t(B) * kCap);
-  t.rinfo = c.take<int32_t>(size_t(B));
   if (S) {
     t.mode = S->mode;
     t.flags = S->flags;
@@ -2608,17 +2184,11 @@ int sparse_items(SparseState& S, const int32_t* tree_ptr, const int64_t* rootind
   return BGCN_OK;
 }
 
-int sparse_conv2(SparseState& S, const float* H1, const int32_t* tree_ptr, const int64_t* rootindex,
-                 float* Z2, KeepSrc keep, hipStream_t s) {
-  if (BGCN_C2_HALF)
-    hipLaunchKernelGGL(k_conv2_half, dim3(unsigned(2 * S.max_items), 2), dim3(256), 0, s, S, H1, Z2, keep);
-  else
-    hipLaunchKernelGGL(k_conv2_sparse, dim3(unsigned(S.max_items), 2), dim3(256), 0, s, S, H1,
-                       tree_ptr, rootindex, Z2, keep);
+int sparse_conv2(SparseState& S, const float* H1, float* Z2, KeepSrc keep, hipStream_t s) {
+  hipLaunchKernelGGL(k_conv2_half, dim3(unsigned(2 * S.max_items), 2), dim3(256), 0, s, S, H1, Z2, keep);
   BGCN_CHECK_LAUNCH();
   return BGCN_OK;
 }
-
 
 int sparse_csc(SparseState& S, hipStream_t s) {
   const int R = int((S.N + kRowBlock - 1) / kRowBlock);
@@ -2801,17 +2371,7 @@ int sparse_prepare(const Prepared& p, int64_t N, int64_t B, int64_t F, int mode,
                    const int64_t* batch, const int64_t* rootindex, const void* X, int xdt, int64_t ldx,
                    hipStream_t s, int part, const bgcn_batch* csr) {
   SparseState S{};
-  S.mode = mode;
-  S.N = N; S.F = F; S.B = B;
-  S.max_items = int(N / kChunk + B + 1);
-  S.flags = p.x_flags; S.nnz = p.x_nnz; S.cols = p.x_cols; S.vals = p.x_vals;
-  S.item_tree = p.item_tree; S.tree_item0 = p.tree_item0;
-  S.item_beg = p.item_beg; S.item_end = p.item_end; S.item_root = p.item_root;
-  S.hist = p.hist; S.col_total = p.col_total; S.col_start = p.col_start; S.col_end = p.col_end;
-  S.csc = p.csc;
-  S.ovf_off = p.x_ovf_off; S.ovf = p.x_ovf; S.ovf_cap = p.ovf_cap; S.long_rows = p.x_long;
-  S.root_map = p.node_root;
-  S.bstatus = p.status;
+  prepared_state(p, N, B, F, mode, S);
   if (!(part & 1)) return mode == 1 ? BGCN_OK : sparse_csc(S, s);
   const int nR = int((N + 255) / 256), nP = int((B + 1 + 255) / 256);
   hipLaunchKernelGGL(k_prologue, dim3(unsigned(nR + nP)), dim3(256), 0, s, S, nullptr, nullptr,
@@ -2834,26 +2394,11 @@ int sparse_prepare(const Prepared& p, int64_t N, int64_t B, int64_t F, int mode,
   return (part & 2) ? sparse_csc(S, s) : BGCN_OK;
 }
 
-int sparse_conv1_gather(SparseState& S, float* Z1, hipStream_t s, const int64_t* rootindex, float sc) {
-  // conv2's root images ride in this launch (BGCN_C2_HALF, BGCN_C2_RIMG; rootindex given)
-  const int nroot = (BGCN_C2_HALF && BGCN_C2_RIMG && rootindex) ? int(2 * S.B) : 0;
-  S.rimg_ready = nroot > 0 ? 1 : 0;
-#if BGCN_C1_MODE == 1
-  hipLaunchKernelGGL(k_conv1_rows2<8>, dim3(nroot + kLongRowBlocks + grid_for(S.N, 8)), dim3(256), 0, s, S, Z1,
-                     rootindex, sc, nroot);
-#elif BGCN_C1_MODE == 2
-  hipLaunchKernelGGL(k_conv1_rows2<4>, dim3(nroot + kLongRowBlocks + grid_for(S.N, 8)), dim3(256), 0, s, S, Z1,
-                     rootindex, sc, nroot);
-#else
-  S.rimg_ready = 0;
-  hipLaunchKernelGGL(k_conv1_gather, dim3(grid_for(S.N, (kC1Threads / 64) * kC1Rows)), dim3(kC1Threads), 0, s,
-                     S, Z1);
-#endif
+int sparse_conv1_gather(SparseState& S, float* Z1, hipStream_t s) {
+  hipLaunchKernelGGL(k_conv1_rows2<4>, dim3(kLongRowBlocks + grid_for(S.N, 8)), dim3(256), 0, s, S, Z1);
   BGCN_CHECK_LAUNCH();
   return BGCN_OK;
 }
-
-
 
 }  // namespace bgcn
 

@@ -143,9 +143,6 @@ __device__ __forceinline__ float4 tree_scale(const SpmmSign& sg, int64_t b, int 
   return make_float4(dh.x / cnt, dh.y / cnt, dh.z / cnt, dh.w / cnt);
 }
 
-#ifndef BGCN_SIGN_XT
-#define BGCN_SIGN_XT 1   // A/B only: 0 drops the cross-tree check (wrong for edges across trees)
-#endif
 // kXt (kSign with an edge across trees: the graph build's BGCN_STATUS_CROSS_TREE, never set
 // by PyG collation): every gathered row is scaled by its own tree, the output row not.  The
 // kernel branches on the status word once per block into separate instantiations: a
@@ -314,7 +311,7 @@ __global__ __launch_bounds__(kRowsThreads) __attribute__((amdgpu_waves_per_eu(BG
   const int hoff = blockIdx.y == 0 ? kHeadIn / 2 : 0;   // kSign: TD's r1 block sits after BU's
   const uint64_t* sgn = sb.sg.sgn + blockIdx.y;      // kSign: this problem's word of row j
   __shared__ float4 red[kRowsGroups][16];
-  const bool xt = kSign && BGCN_SIGN_XT && (*sb.sg.tree_status[blockIdx.y] & BGCN_STATUS_CROSS_TREE) != 0;
+  const bool xt = kSign && (*sb.sg.tree_status[blockIdx.y] & BGCN_STATUS_CROSS_TREE) != 0;
   if (int64_t(blockIdx.x) < nchunk) {
     // XCD-contiguous chunk ranges: a tree's rows and the neighbours they gather stay in one
     // L2 (the launch pads gridDim.x to a multiple of 8)
