@@ -34,6 +34,7 @@ BGCN_DTYPE_F32 = 0
 BGCN_DTYPE_BF16 = 1
 ABI_VERSION = 12   # BGCN_ABI_VERSION of include/bgcn.h
 BGCN_STATUS_CROSS_TREE = 16
+BGCN_EDGE_INFER_TILE = 32   # edges per workgroup of bgcn_edge_infer
 
 # every symbol include/bgcn.h declares (checked by tests/test_capi.py)
 EXPORTED_SYMBOLS = (
@@ -54,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "bgcn_weight_images_size", "bgcn_train_step_saved", "bgcn_eval_step",
     "bgcn_loader_create", "bgcn_loader_slot_bytes", "bgcn_loader_len", "bgcn_loader_next", "bgcn_loader_destroy",
     "bgcn_loader_wait", "bgcn_loader_get_stats",
+    "bgcn_bn_fold", "bgcn_edge_infer", "bgcn_ebgcn_conv2_lin_workspace_size", "bgcn_ebgcn_conv2_lin",
 )
 
 
@@ -201,6 +203,13 @@ _SIGS = {
     "bgcn_loader_destroy": (None, [c_void_p]),
     "bgcn_loader_wait": (c_int, [c_void_p]),
     "bgcn_loader_get_stats": (c_int, [c_void_p, c_void_p, c_int]),
+    "bgcn_bn_fold": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_void_p, c_void_p]),
+    "bgcn_edge_infer": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "bgcn_ebgcn_conv2_lin_workspace_size": (c_size_t, [c_int64, c_int64, c_int64]),
+    "bgcn_ebgcn_conv2_lin": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
+                                     c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

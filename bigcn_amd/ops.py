@@ -6,6 +6,9 @@
 * :func:`gcn_conv` - PyG-2.x ``GCNConv.forward`` (lin -> propagate -> +bias) with a
   HIP backward (K2, K3, K4, K10).
 * :func:`scatter_mean` - ``torch_scatter.scatter_mean`` (K8).
+* :func:`edge_infer` / :func:`ebgcn_conv2_lin` - what EBGCN's eval forward adds
+  (``model/Twitter/EBGCN.py:72-116``): the edge-inference kernel and conv2's lin over the
+  BatchNorm'd concat.
 * :func:`bigcn_encoder` - the fused TD+BU encoder of ``BiGCN.forward``
   (``model/Twitter/BiGCN_Twitter.py:125-128``), all of K1-K10 on the GPU.
 
@@ -430,6 +433,99 @@ def scatter_mean(src: torch.Tensor, index: torch.Tensor, dim: int = 0, out=None,
         out.copy_(res)
         return out
     return res
+
+
+# ----------------------------------------------------------------------------- EBGCN (eval)
+EDGE_INFER_TILE = _lib.BGCN_EDGE_INFER_TILE   # edges per workgroup of the edge-inference kernel
+_NO_TRAINING = ("bigcn_amd's EBGCN is the inference-only path (eval mode): training - batch-statistics "
+                "BatchNorm, the Bayesian edge branch and its KL loss, the backward - is not implemented")
+
+
+def bn_fold(bn: torch.nn.Module):
+    """An eval-mode ``BatchNorm1d`` as ``y = g x + t`` (``bgcn_bn_fold``): ``g = weight /
+    sqrt(running_var + eps)``, ``t = bias - running_mean g``; returns ``(g, t)``."""
+    if bn.running_mean is None or bn.weight is None:
+        raise ValueError("bn_fold needs an affine BatchNorm with running statistics")
+    ps = [q.detach().to(torch.float32).contiguous() for q in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+    _dev_check(*ps)
+    C = ps[0].numel()
+    gt = torch.empty(2, C, dtype=torch.float32, device=ps[0].device)
+    check(_lib.lib().bgcn_bn_fold(*(ptr(q) for q in ps), float(bn.eps), C, ptr(gt[0]), ptr(gt[1]), stream_handle()))
+    return gt[0], gt[1]
+
+
+def _f32c(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().to(torch.float32).contiguous()
+
+
+def edge_infer(h: torch.Tensor, edge_index: torch.Tensor, direction_module, validate: bool = False,
+               status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``edge_pred`` [E] of ``direction_module.edge_infer(h, edge_index)`` (``EBGCN.py:95-116``)
+    in eval mode, on the edge-inference kernel (``bgcn_edge_infer``); the Bayesian branch, which
+    only feeds the edge loss, is not run.
+
+    ``h`` [N, 64] is conv1's output, ``direction_module`` a ``TDrumorGCN`` / ``BUrumorGCN`` of
+    :mod:`bigcn_amd.ebgcn` (anything with the reference's ``sim_network`` and ``fc1``).  As in
+    the reference, edge ``(r, c)`` reads the rows ``h[r - 1]`` and ``h[c - 1]`` (0 wraps to the
+    last node).  An edge with an index outside [0, N) gets 0 and sets ``status`` (an int32 [1]
+    device tensor, optional) to 1; ``validate=True`` syncs and raises IndexError instead."""
+    if direction_module.training:
+        raise NotImplementedError(_NO_TRAINING)
+    conv, norm, _act, conv_out = direction_module.sim_network
+    fc1 = direction_module.fc1.weight
+    _dev_check(h, edge_index, fc1)
+    ei = _check_ei(edge_index)
+    if h.dim() != 2:
+        raise ValueError("h must be [N, hidden]")
+    h = _f32c(h) if (h.dtype != torch.float32 or h.stride(1) != 1 or h.requires_grad) else h
+    N, H = h.shape
+    E = int(ei.size(1))
+    K = int(fc1.size(0))
+    if conv.weight.shape != (H, H, 1) or conv_out.weight.shape != (1, H, 1) or fc1.shape != (K, H):
+        raise ValueError("direction_module's sim_network / fc1 do not match h's hidden size")
+    pred = torch.empty(E, dtype=torch.float32, device=h.device)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=h.device)
+    g, t = bn_fold(norm)
+    wc, wo, bo, f1 = _f32c(conv.weight), _f32c(conv_out.weight), _f32c(conv_out.bias), _f32c(fc1)
+    check(_lib.lib().bgcn_edge_infer(ptr(h), h.stride(0), N, H, ptr(ei), E, ptr(wc), ptr(g), ptr(t), ptr(wo),
+                                     ptr(bo), ptr(f1), K, ptr(pred), ptr(status), stream_handle()))
+    if validate and int(status.item()) & 1:
+        raise IndexError("edge_index contains an index out of range [0, num_nodes)")
+    return pred
+
+
+def ebgcn_conv2_lin(h1: torch.Tensor, x: torch.Tensor, batch: torch.Tensor, rootindex: torch.Tensor,
+                    weight: torch.Tensor, bn1: Optional[torch.nn.Module], validate: bool = False,
+                    status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv2's lin of the eval-mode EBGCN direction (``EBGCN.py:72-84``): ``relu(bn1(cat(h1,
+    x[root of the node's tree]))) W2^T`` [N, 64], the root block's F-wide product done once per
+    tree (``bgcn_ebgcn_conv2_lin``).  ``bn1=None`` skips the BatchNorm (the reference's one-node
+    batch).  A rootindex outside [0, N) or a batch id outside [0, B) contributes zeros and sets
+    ``status`` (int32 [1], optional) to 1; ``validate=True`` syncs and raises IndexError."""
+    _dev_check(h1, x, batch, rootindex, weight)
+    h1, x, w2 = _f32c(h1), _f32c(x), _f32c(weight)
+    batch, rootindex = batch.to(torch.int64).contiguous(), rootindex.to(torch.int64).contiguous()
+    N, H = h1.shape
+    F, B = int(x.size(1)), int(rootindex.numel())
+    if x.size(0) != N or batch.numel() != N or w2.shape != (H, H + F):
+        raise ValueError("ebgcn_conv2_lin: shapes do not match (h1 [N, 64], x [N, F], batch [N], W2 [64, 64 + F])")
+    if N == 0:
+        return h1.new_empty(0, H)
+    g, t = bn_fold(bn1) if bn1 is not None else (None, None)
+    if g is not None and g.numel() != H + F:
+        raise ValueError("bn1 must cover the [hidden + input] concat")
+    z2 = torch.empty(N, H, dtype=torch.float32, device=h1.device)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=h1.device)
+    L = _lib.lib()
+    ws = workspace(L.bgcn_ebgcn_conv2_lin_workspace_size(N, B, F), h1.device)
+    check(L.bgcn_ebgcn_conv2_lin(ptr(h1), h1.stride(0), ptr(x), x.stride(0), ptr(batch), ptr(rootindex), N, B, F, H,
+                                 ptr(w2), ptr(g), ptr(t), ptr(z2), H, ptr(status), ptr(ws), ws.numel(),
+                                 stream_handle()))
+    if validate and int(status.item()) & 1:
+        raise IndexError("rootindex / batch contains an index out of range")
+    return z2
 
 
 # ----------------------------------------------------------------------------- fused encoder

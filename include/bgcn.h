@@ -211,6 +211,55 @@ int bgcn_head_backward(const float* head_in, const float* logp, const float* dlo
                        float* fc_db, bgcn_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * EBGCN (model/Twitter/EBGCN.py), eval mode: the two operations it adds over BiGCN.  Everything
+ * else of its forward is the entry points above (conv1, bgcn_build_graph with edge_weight =
+ * edge_pred + bgcn_spmm for conv2's aggregation, bgcn_scatter_mean_fwd, bgcn_head_forward).
+ * Additive entry points: BGCN_ABI_VERSION is unchanged.
+ *
+ * bgcn_bn_fold: an eval-mode BatchNorm1d as one multiply-add per channel,
+ *   g = gamma / sqrt(running_var + eps),  t = beta - running_mean * g      (y = g x + t).
+ *
+ * bgcn_edge_infer: edge_pred of TDrumorGCN.edge_infer / BUrumorGCN.edge_infer (EBGCN.py:95-116,
+ * :189-212) without the Bayesian branch (its only product, the KL edge loss, is dropped by the
+ * evaluation loop, :338).  h [N, 64] (ld ldh) = conv1's output; edge_index int64 [2, E];
+ * conv_w [64, 64] = sim_valconv0.weight; (bn_g, bn_t) [64] = sim_valnorm0 folded by bgcn_bn_fold;
+ * out_w [64], out_b [1] = sim_valconv_out; fc1_w [edge_num, 64]; edge_pred [E].
+ * Per edge e, with a = h[(row_e - 1) mod N] and b = h[(col_e - 1) mod N] - the reference's
+ * `x[row - 1]` as written: ids are read one lower than the edge list says and id 0 reads the
+ * LAST node - :
+ *   D[c][l] = |a[c] - b[l]|;  Y = conv_w D;  Z = leaky_relu(bn_g[o] Y[o][l] + bn_t[o], 0.01);
+ *   s[l] = sum_o out_w[o] Z[o][l] + out_b;  edge_pred[e] = mean_k sigmoid(sum_l fc1_w[k][l] s[l]).
+ * The 64 x 64 x 64 product per edge runs on the fp32 MFMA with D generated in registers (about
+ * 512 B read and 4 B written per edge); one workgroup takes BGCN_EDGE_INFER_TILE edges.
+ * Deterministic, no workspace.  hid must be 64 and 1 <= edge_num <= 8 (else BGCN_EINVAL).  An
+ * edge with an end outside [0, N) reads nothing, gets edge_pred 0 and sets *status to 1.
+ *
+ * bgcn_ebgcn_conv2_lin: conv2's lin over relu(bn1(cat(h1, x[root of the node's tree])))
+ * (EBGCN.py:72-84; no dropout, as in the reference's EBGCN forward):
+ *   z2[i] = relu(g_h . h1[i] + t_h) W2[:, :64]^T + r[batch[i]]
+ *   r[b]  = relu(g_x . x[rootindex[b]] + t_x) W2[:, 64:]^T      (once per tree, not per node)
+ * (bn_g, bn_t) [64 + F] = bn1 folded, g_h / g_x its first 64 / last F channels; both NULL = bn1
+ * skipped (the reference's one-node batch, :80).  w2 [64, 64 + F] = conv2.lin.weight; x [N, F]
+ * fp32; z2 [N, 64].  hid must be 64 and F a multiple of 4 (else BGCN_EINVAL).  A rootindex
+ * outside [0, N) or a batch id outside [0, B) contributes zeros and sets *status to 1.
+ * -------------------------------------------------------------------------- */
+#define BGCN_EDGE_INFER_TILE 32
+int bgcn_bn_fold(const float* gamma, const float* beta, const float* running_mean,
+                 const float* running_var, float eps, int64_t channels, float* g, float* t,
+                 bgcn_stream_t stream);
+int bgcn_edge_infer(const float* h, int64_t ldh, int64_t num_nodes, int64_t hid,
+                    const int64_t* edge_index, int64_t num_edges, const float* conv_w,
+                    const float* bn_g, const float* bn_t, const float* out_w, const float* out_b,
+                    const float* fc1_w, int32_t edge_num, float* edge_pred, int32_t* status,
+                    bgcn_stream_t stream);
+size_t bgcn_ebgcn_conv2_lin_workspace_size(int64_t num_nodes, int64_t num_graphs, int64_t in_feats);
+int bgcn_ebgcn_conv2_lin(const float* h1, int64_t ldh, const float* x, int64_t ldx,
+                         const int64_t* batch, const int64_t* rootindex, int64_t num_nodes,
+                         int64_t num_graphs, int64_t in_feats, int64_t hid, const float* w2,
+                         const float* bn_g, const float* bn_t, float* z2, int64_t ldz, int32_t* status,
+                         void* workspace, size_t workspace_bytes, bgcn_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * DropEdge (Process/dataset.py:68-90): per tree, keep a uniform random subset of
  * exactly int(E_t * (1 - droprate)) edges (count computed in double as Python does),
  * in their original order; droprate <= 0 keeps every edge (the reference's
