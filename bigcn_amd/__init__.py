@@ -7,6 +7,8 @@ Drop-in symbols for the reference's hot path (cwkd/BiGCN):
 * ``TDrumorGCN``, ``BUrumorGCN``, ``BiGCN`` (Twitter, 4 classes), ``Net`` (Weibo, 2 classes)
 * ``EBGCN`` - the edge-enhanced model (model/Twitter/EBGCN.py) for inference: eval forward on
   the edge-inference kernel (``edge_infer``), reference checkpoints load strictly
+* ``explain`` / ``segment_rank`` - the reference's analysis (explain_PHEME.py): per-stage node sums and
+  per-tree rankings of a whole batch, for ``BiGCN`` / ``Net`` / ``EBGCN`` in eval mode
 * ``FusedTrainStep`` - the training-loop body (BiGCN_Twitter.py:183-189) as one native call
   + the data-parallel all-reduce + fused Adam
 
@@ -15,11 +17,12 @@ all backed by hand-written HIP kernels in ``libbgcn.so`` (C ABI: ``include/bgcn.
 from .bigcn import BiGCN, BUrumorGCN, Net, TDrumorGCN, make_optimizer
 from .conv import GCNConv
 from .ebgcn import EBGCN
+from .explain import explain, segment_rank
 from .ops import Graph, bigcn_encoder, build_graph, edge_infer, gcn_conv, scatter_mean, spmm
 from .optim import FusedAdam, bigcn_adam
 from .train import FusedTrainStep
 
 __all__ = ["GCNConv", "scatter_mean", "TDrumorGCN", "BUrumorGCN", "BiGCN", "Net", "make_optimizer",
            "Graph", "build_graph", "gcn_conv", "spmm", "bigcn_encoder", "FusedAdam", "bigcn_adam",
-           "FusedTrainStep", "EBGCN", "edge_infer"]
+           "FusedTrainStep", "EBGCN", "edge_infer", "explain", "segment_rank"]
 __version__ = "0.1.0"

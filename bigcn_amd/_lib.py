@@ -35,6 +35,7 @@ BGCN_DTYPE_BF16 = 1
 ABI_VERSION = 12   # BGCN_ABI_VERSION of include/bgcn.h
 BGCN_STATUS_CROSS_TREE = 16
 BGCN_EDGE_INFER_TILE = 32   # edges per workgroup of bgcn_edge_infer
+BGCN_SEGMENT_RANK_LDS = 4096   # longest segment bgcn_segment_rank sorts in LDS
 
 # every symbol include/bgcn.h declares (checked by tests/test_capi.py)
 EXPORTED_SYMBOLS = (
@@ -56,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "bgcn_loader_create", "bgcn_loader_slot_bytes", "bgcn_loader_len", "bgcn_loader_next", "bgcn_loader_destroy",
     "bgcn_loader_wait", "bgcn_loader_get_stats",
     "bgcn_bn_fold", "bgcn_edge_infer", "bgcn_ebgcn_conv2_lin_workspace_size", "bgcn_ebgcn_conv2_lin",
+    "bgcn_explain_sums_workspace_size", "bgcn_explain_sums", "bgcn_segment_rank_workspace_size", "bgcn_segment_rank",
 )
 
 
@@ -210,6 +212,13 @@ _SIGS = {
     "bgcn_ebgcn_conv2_lin": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
                                      c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                      c_void_p, c_size_t, c_void_p]),
+    "bgcn_explain_sums_workspace_size": (c_size_t, [c_int64]),
+    "bgcn_explain_sums": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                  c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_size_t, c_void_p]),
+    "bgcn_segment_rank_workspace_size": (c_size_t, [c_int64]),
+    "bgcn_segment_rank": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_size_t, c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

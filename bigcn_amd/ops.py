@@ -9,6 +9,8 @@
 * :func:`edge_infer` / :func:`ebgcn_conv2_lin` - what EBGCN's eval forward adds
   (``model/Twitter/EBGCN.py:72-116``): the edge-inference kernel and conv2's lin over the
   BatchNorm'd concat.
+* :func:`explain_sums` / :func:`segment_rank` - the reference's analysis (``explain_PHEME.py``):
+  per-node stage sums without the concat, and a batched per-tree ``topk(k = n)``.
 * :func:`bigcn_encoder` - the fused TD+BU encoder of ``BiGCN.forward``
   (``model/Twitter/BiGCN_Twitter.py:125-128``), all of K1-K10 on the GPU.
 
@@ -526,6 +528,85 @@ def ebgcn_conv2_lin(h1: torch.Tensor, x: torch.Tensor, batch: torch.Tensor, root
     if validate and int(status.item()) & 1:
         raise IndexError("rootindex / batch contains an index out of range")
     return z2
+
+
+# ----------------------------------------------------------------------------- explain
+SEGMENT_RANK_LDS = _lib.BGCN_SEGMENT_RANK_LDS   # longest segment the ranking sorts in LDS
+# the reference's stage keys (explain_PHEME.py:91-242), in its order
+STAGES_BIGCN = ("conv1_output_sum", "conv1_output_cat_x_sum", "conv2_input_sum", "conv2_output_sum",
+                "scatter_mean_input_sum")
+STAGES_EBGCN = STAGES_BIGCN[:2] + ("conv1_output_cat_x_bn1_sum",) + STAGES_BIGCN[2:]
+
+
+def explain_sums(h1: torch.Tensor, h2: torch.Tensor, x: torch.Tensor, batch: torch.Tensor, rootindex: torch.Tensor,
+                 bn1: Optional[torch.nn.Module] = None, want_x_sum: bool = True, validate: bool = False,
+                 status: Optional[torch.Tensor] = None):
+    """``(sums [S, N], x_sum [N] or None)``: the per-node stage sums of one direction
+    (``bgcn_explain_sums``; ``explain_PHEME.py:91-242``) from conv1's output ``h1`` [N, 64], conv2's
+    output before its relu ``h2`` [N, 64] and the features ``x`` [N, F].  ``bn1=None`` gives the
+    BiGCN stage list (:data:`STAGES_BIGCN`, S = 5), a ``BatchNorm1d(64 + F)`` the EBGCN one
+    (:data:`STAGES_EBGCN`, S = 6).  ``x_sum`` is the row sum of ``x`` (``want_x_sum=False`` skips
+    that pass over X).  A rootindex outside [0, N) or a batch id outside [0, B) contributes zeros
+    and sets ``status`` (int32 [1], optional) to 1; ``validate=True`` syncs and raises IndexError."""
+    _dev_check(h1, h2, x, batch, rootindex)
+    h1, h2, x = _f32c(h1), _f32c(h2), _f32c(x)
+    batch, rootindex = batch.to(torch.int64).contiguous(), rootindex.to(torch.int64).contiguous()
+    N, H = h1.shape
+    F, B = int(x.size(1)), int(rootindex.numel())
+    if h2.shape != (N, H) or x.size(0) != N or batch.numel() != N:
+        raise ValueError("explain_sums: shapes do not match (h1, h2 [N, 64], x [N, F], batch [N])")
+    g, t = bn_fold(bn1) if bn1 is not None else (None, None)
+    if g is not None and g.numel() != H + F:
+        raise ValueError("bn1 must cover the [hidden + input] concat")
+    S = len(STAGES_BIGCN if g is None else STAGES_EBGCN)
+    sums = torch.empty(S, N, dtype=torch.float32, device=h1.device)
+    x_sum = torch.empty(N, dtype=torch.float32, device=h1.device) if want_x_sum else None
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=h1.device)
+    L = _lib.lib()
+    ws = workspace(L.bgcn_explain_sums_workspace_size(B), h1.device)
+    check(L.bgcn_explain_sums(ptr(h1), h1.stride(0), ptr(h2), h2.stride(0), ptr(x), x.stride(0), ptr(batch),
+                              ptr(rootindex), N, B, F, H, ptr(g), ptr(t), ptr(sums), N, ptr(x_sum), ptr(status),
+                              ptr(ws), ws.numel(), stream_handle()))
+    if validate and int(status.item()) & 1:
+        raise IndexError("rootindex / batch contains an index out of range")
+    return sums, x_sum
+
+
+def _segment_rank(values: torch.Tensor, batch: torch.Tensor, num_graphs: int, status: torch.Tensor):
+    _dev_check(values, batch)
+    if values.dim() == 1:
+        values = values.unsqueeze(0)
+    if values.dim() != 2 or values.size(1) != batch.numel():
+        raise ValueError("segment_rank: values must be [S, N] (or [N]) with batch [N]")
+    if values.dtype != torch.float32 or values.stride(1) != 1 or values.requires_grad:
+        values = _f32c(values)
+    batch = batch.to(torch.int64).contiguous()
+    S, N = values.shape
+    ld = values.stride(0) if S > 1 else max(N, 1)
+    order = torch.empty(S, N, dtype=torch.int32, device=values.device)
+    srt = torch.empty(S, N, dtype=torch.float32, device=values.device)
+    L = _lib.lib()
+    ws = workspace(L.bgcn_segment_rank_workspace_size(int(num_graphs)), values.device)
+    check(L.bgcn_segment_rank(ptr(values), ld, S, ptr(batch), N, int(num_graphs), ptr(order), ptr(srt), ptr(status),
+                              ptr(ws), ws.numel(), stream_handle()))
+    return order, srt
+
+
+def segment_rank(values: torch.Tensor, batch: torch.Tensor, num_graphs: int):
+    """``(order int32 [S, N], sorted fp32 [S, N])``: ``torch.topk(values[s, tree], k = n)`` for
+    every row ``s`` of ``values`` [S, N] and every tree of the PyG batch vector ``batch`` [N]
+    (``bgcn_segment_rank``).  Inside tree t's node range ``order`` holds the tree's local node
+    indices (node id minus the tree's first node) by descending value and ``sorted`` the values in
+    that order.  Equal values rank by ascending node index (-0.0 equals +0.0); NaN ranks above
+    +inf, NaNs among themselves by ascending index.  ``values`` may have any row stride.  One host
+    sync at the end: a ``batch`` that decreases, or holds an id outside [0, num_graphs), raises
+    IndexError."""
+    status = torch.zeros(1, dtype=torch.int32, device=values.device)
+    order, srt = _segment_rank(values, batch, num_graphs, status)
+    if int(status.item()) & 1:
+        raise IndexError("segment_rank: batch must be non-decreasing with ids in [0, num_graphs)")
+    return order, srt
 
 
 # ----------------------------------------------------------------------------- fused encoder

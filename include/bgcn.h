@@ -260,6 +260,54 @@ int bgcn_ebgcn_conv2_lin(const float* h1, int64_t ldh, const float* x, int64_t l
                          void* workspace, size_t workspace_bytes, bgcn_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * Explain (explain_PHEME.py:91-242, :530-533), inference only: after every stage of a direction
+ * each node's activation row is summed to one number and the nodes of a tree are ranked by it.
+ * Additive entry points: BGCN_ABI_VERSION is unchanged.
+ *
+ * bgcn_explain_sums: the per-node stage sums of one direction, sums [S, num_nodes] (row stride
+ * ld_sums), stage-major.  h1 [N, 64] = conv1's output, h2 [N, 64] = conv2's output BEFORE its
+ * relu, x [N, F] fp32; (bn_g, bn_t) [64 + F] = bn1 folded by bgcn_bn_fold (g_h / g_x its first
+ * 64 / last F channels), both NULL = the BiGCN stage list.  With r = rootindex[batch[n]]:
+ *   S = 5 (BiGCN)                              S = 6 (EBGCN)
+ *   0 sum h1[n]                                0 sum h1[n]
+ *   1 sum h1[n] + sum x[r]                     1 sum h1[n] + sum x[r]
+ *   2 sum relu(h1[n]) + sum relu(x[r])         2 sum (g_h h1[n] + t_h) + sum (g_x x[r] + t_x)
+ *   3 sum h2[n]                                3 sum relu(g_h h1[n] + t_h) + sum relu(g_x x[r] + t_x)
+ *   4 sum relu(h2[n]) + sum h1[r]              4 sum h2[n]
+ *                                              5 sum relu(h2[n]) + sum h1[r]
+ * (the reference's conv1_output_sum, conv1_output_cat_x_sum, [conv1_output_cat_x_bn1_sum,]
+ * conv2_input_sum, conv2_output_sum, scatter_mean_input_sum; eval-mode dropout is the identity).
+ * No concat is materialised and every root term is computed once per tree.  x_sum [N] (optional,
+ * NULL = skip) receives sum_f x[n][f]: the one pass over all of X, one wave per row with 16-byte
+ * streaming loads.  Deterministic (fixed summation order, no float atomics).  hid must be 64 and
+ * F a multiple of 4 (else BGCN_EINVAL).  A rootindex outside [0, N) or a batch id outside [0, B)
+ * is not read, contributes zeros and sets *status bit 0.
+ *
+ * bgcn_segment_rank: torch.topk(values, k = n) per tree and stage.  values [S, N] fp32 (row
+ * stride ld); batch int64 [N], the PyG batch vector (non-decreasing; tree ids without nodes are
+ * fine); order int32 [S, N] and sorted fp32 [S, N] (row stride N).  Tree t's slots are its node
+ * range: order holds the tree's LOCAL node indices (node id minus the tree's first node) by
+ * descending value, sorted the values in that order (bit copies).  The order is total: equal
+ * values by ascending node index, -0.0 equal to +0.0, every NaN above +inf (as torch) and NaNs
+ * among themselves by ascending index.  Segment bounds are derived on the device.  A segment of
+ * at most BGCN_SEGMENT_RANK_LDS nodes is sorted in LDS by one workgroup per (stage, tree); longer
+ * ones are ranked by counting through global memory (O(n^2) compares, any length).
+ * Deterministic.  A batch vector that decreases anywhere, or holds an id outside [0, B), sets
+ * *status bit 0; the outputs are then left unwritten.
+ * -------------------------------------------------------------------------- */
+#define BGCN_SEGMENT_RANK_LDS 4096
+size_t bgcn_explain_sums_workspace_size(int64_t num_graphs);
+int bgcn_explain_sums(const float* h1, int64_t ldh1, const float* h2, int64_t ldh2, const float* x,
+                      int64_t ldx, const int64_t* batch, const int64_t* rootindex, int64_t num_nodes,
+                      int64_t num_graphs, int64_t in_feats, int64_t hid, const float* bn_g,
+                      const float* bn_t, float* sums, int64_t ld_sums, float* x_sum, int32_t* status,
+                      void* workspace, size_t workspace_bytes, bgcn_stream_t stream);
+size_t bgcn_segment_rank_workspace_size(int64_t num_graphs);
+int bgcn_segment_rank(const float* values, int64_t ld, int64_t num_stages, const int64_t* batch,
+                      int64_t num_nodes, int64_t num_graphs, int32_t* order, float* sorted,
+                      int32_t* status, void* workspace, size_t workspace_bytes, bgcn_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * DropEdge (Process/dataset.py:68-90): per tree, keep a uniform random subset of
  * exactly int(E_t * (1 - droprate)) edges (count computed in double as Python does),
  * in their original order; droprate <= 0 keeps every edge (the reference's
