@@ -751,7 +751,7 @@ size_t carve_fused(Carve& c, int64_t N, int64_t B, int64_t F, FusedWs* w) {
   // dense feature mode: node splits of >= 2048 nodes, at most 32 (its dW2 blocks loop over
   // a split's nodes: 8 splits left 400+ serial k-tiles per block at Weibo size)
   {
-    static const int64_t kd_env = [] { const char* e = std::getenv("BGCN_DW2D_NODES"); return e ? int64_t(atol(e)) : 0; }();
+    const int64_t kd_env = BGCN_KNOB_ONCE("BGCN_DW2D_NODES", 0);
     int64_t kd = kd_env > 0 ? kd_env : std::max<int64_t>(2048, (N + 31) / 32);   // (env: A/B runs)
     kd = (kd + 63) / 64 * 64;
     t.kchunk2d = kd;
@@ -871,8 +871,7 @@ static bool readout_sign(const bgcn_bigcn_args* a, const SparseState& sp, FusedW
   // aggregation to per-neighbour tree scales on the device); unchecked graphs keep
   // k_readout_bwd, which handles any edge set
   if (!w.tree_status[0] || !w.tree_status[1]) return false;
-  const char* e = std::getenv("BGCN_READOUT_SIGN");
-  if (e && atoi(e) == 0) return false;
+  if (knob("BGCN_READOUT_SIGN", 1) == 0) return false;
   const SpmmBatch sb = pair_batch(a->td, a->bu, true, a->num_nodes, nullptr, nullptr, nullptr, nullptr,
                                   BGCN_EPI_NONE, w);
   return spmm_planned(sb, 2);
@@ -914,13 +913,7 @@ static int setup(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, FusedWs& w
   w.tree_status[1] = prep ? prep->status : a->bu.tree_status;
   if (prep) {   // the batch's weight-independent state lives in the prepared buffer
     w.node_root = prep->node_root;
-    sp.item_tree = prep->item_tree; sp.tree_item0 = prep->tree_item0;
-    sp.item_beg = prep->item_beg; sp.item_end = prep->item_end; sp.item_root = prep->item_root;
-    sp.hist = prep->hist; sp.col_total = prep->col_total;
-    sp.col_start = prep->col_start; sp.col_end = prep->col_end;
-    sp.csc = prep->csc;
-    sp.ovf_off = prep->x_ovf_off; sp.ovf = prep->x_ovf; sp.ovf_cap = prep->ovf_cap;
-    sp.long_rows = prep->x_long;
+    bind_prepared(*prep, sp);
   }
   // dense kernels run when feat_mode == dense (no gate) or when the sparse path overflowed
   // (auto); under BGCN_FEAT_SPARSE they are not launched (dense_launched)
@@ -932,8 +925,8 @@ static int setup(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, FusedWs& w
 // read once, keeps the f32 MFMA forms), fp32 X split three ways, six products
 // (BGCN_GEMM_X6=0, read once, keeps the f32 MFMA forms); 16-byte X rows and W2 rows
 static bool bf16_mfma_ok(const bgcn_bigcn_args* a) {
-  static const bool b16 = [] { const char* e = std::getenv("BGCN_GEMM_BF16"); return !(e && atoi(e) == 0); }();
-  static const bool x6 = [] { const char* e = std::getenv("BGCN_GEMM_X6"); return !(e && atoi(e) == 0); }();
+  const bool b16 = BGCN_KNOB_ONCE("BGCN_GEMM_BF16", 1) != 0;
+  const bool x6 = BGCN_KNOB_ONCE("BGCN_GEMM_X6", 1) != 0;
   return (a->x_dtype == BGCN_DTYPE_BF16 ? b16 : x6) && a->in_feats % 8 == 0 && a->ldx % 8 == 0 && (reinterpret_cast<uintptr_t>(a->x) & 15) == 0 &&
          (reinterpret_cast<uintptr_t>(a->td_w2) & 15) == 0 && (reinterpret_cast<uintptr_t>(a->bu_w2) & 15) == 0;
 }
@@ -1099,7 +1092,7 @@ static int forward_tail(const bgcn_bigcn_args* a, FusedWs& w, SparseState& sp, K
 // -> dW1.  Side lane, forked as soon as its inputs exist: db2, the dW2 chain (relu(H1)
 // block, root partials, root columns), db1 and the gated dense dW1; joined at the end.
 int bigcn_backward_impl(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, hipStream_t s,
-                        const Prepared* prep, bool side_busy, const HeadGradJob* head,
+                        const Prepared* prep, const HeadGradJob* head,
                         const WeightImages* img, bool defer_dw1, const TailAdam* adam, bool* adam_done) {
   if (adam_done) *adam_done = false;
   BGCN_TRY(check_args(a, prep != nullptr));
@@ -1163,8 +1156,7 @@ int bigcn_backward_impl(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, hip
   // MFMA launch's 469 at the bench workload; k_dw2_root<float> takes the root factor out of
   // the MFMA operand instead, three products as for bf16 X.  BGCN_DW2_ROOT (read per call,
   // A/B runs and tests): 0 = k_dw2_f32 / k_dw2_bf16, 2 = the root form for any tree size)
-  const char* root_env = std::getenv("BGCN_DW2_ROOT");
-  const int root_mode = root_env ? atoi(root_env) : 1;
+  const int root_mode = int(knob("BGCN_DW2_ROOT", 1));
   const bool root_f32 = root_mode != 0;
   // (the tree-run tiles need trees of >= 32 nodes on average, as conv2's root planes do:
   // PHEME's ~10-node trees left 64-node tiles mostly empty, 15.6 -> 43.2 us)
@@ -1192,8 +1184,7 @@ int bigcn_backward_impl(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, hip
   m.n_dw2 = dw2_own ? 0 : m.n_dw2_dense;   // the sparse relu(H1) block is formed by the dH1 blocks
   // the H1 columns in the root columns' launch (its first blocks), not the middle launch's
   // (there their k-tiles in sequence made it 17 -> 124 us at twitter15 fp32).  BGCN_DW2_H_MID=1: the middle launch
-  const char* h_env = std::getenv("BGCN_DW2_H_MID");
-  const bool h_mid = h_env && atoi(h_env) == 1;
+  const bool h_mid = knob("BGCN_DW2_H_MID", 0) == 1;
   if (dw2b && !h_mid) {
     m.n_dw2h = m.n_dw2_dense;
     m.n_dw2 = 0;
@@ -1255,7 +1246,6 @@ int bigcn_backward_impl(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, hip
   // (the launcher clears adam.on for a tail form that cannot carry it: BGCN_DW1_SPLIT != 0)
   if (adam_done) *adam_done = t.adam.on != 0;
   timing_end(5, s);
-  (void)side_busy;
   timing_end(9, s);   // the main stream's own chain (span class, bgcn_train_step)
   // join only what this backward forked (a next-batch preparation on the side lane is
   // waited for by the next bgcn_train_step call instead)
@@ -1314,7 +1304,7 @@ extern "C" int bgcn_bigcn_backward(const bgcn_bigcn_args* args, void* workspace,
     return bgcn::bigcn_prepared_call(args, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream),
                                      true);
   return bgcn::bigcn_backward_impl(args, workspace, workspace_bytes,
-                                   reinterpret_cast<hipStream_t>(stream), nullptr, false);
+                                   reinterpret_cast<hipStream_t>(stream));
 }
 extern "C" int bgcn_keep_words(uint64_t seed, int64_t num_nodes, int32_t num_words,
                                uint32_t* words, bgcn_stream_t stream) {

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <string>
 
 #include "../../include/bgcn.h"
@@ -37,6 +38,19 @@ inline int propagate(int rc) { return rc; }
   } while (0)
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// ---------------------------------------------------------------- runtime knobs
+// Every BGCN_* environment variable the library reads goes through these (INTEGRATION.md
+// section 7 lists them all).  knob(): the integer value at this call, `unset` when the
+// variable is not set - for knobs that tests flip inside one process.  BGCN_KNOB_ONCE: the
+// same, read the first time its call site runs and kept for the process.
+inline const char* knob_text(const char* name) { return std::getenv(name); }
+inline long knob(const char* name, long unset) {
+  const char* e = knob_text(name);
+  return e ? atol(e) : unset;
+}
+#define BGCN_KNOB_ONCE(name, unset) \
+  ([] { static const long v = ::bgcn::knob(name, unset); return v; }())
 
 // Simple bump allocator over a caller-provided workspace.
 // Blocks are dispatched to the 8 XCDs round-robin (block b of a 1-D grid runs on XCD b % 8).

@@ -962,7 +962,7 @@ int tn_splits(int64_t Mc, int64_t Nc, int64_t K) {
 // k_gemm_tn_w (128 x 128 tiles): node splits for about BGCN_TN_WIDE_BLOCKS blocks (A/B
 // knob, read once; default 1024)
 int tn_splits_w(int64_t Mc, int64_t Nc, int64_t K) {
-  static const int64_t target = [] { const char* e = std::getenv("BGCN_TN_WIDE_BLOCKS"); return e ? std::max<int64_t>(1, atol(e)) : int64_t(1024); }();
+  const int64_t target = std::max<int64_t>(1, BGCN_KNOB_ONCE("BGCN_TN_WIDE_BLOCKS", 1024));
   const int64_t tiles = ((Nc + 127) / 128) * ((Mc + 127) / 128);
   const int64_t want = std::max<int64_t>(1, target / tiles);
   const int64_t maxs = (K + BK - 1) / BK;
@@ -982,11 +982,7 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // read once
 template <class TX>
 static bool bf16_mfma_for() {
-  static const bool on = [] {
-    const char* e = std::getenv(sizeof(TX) == 2 ? "BGCN_GEMM_BF16" : "BGCN_GEMM_X6");
-    return !(e && atoi(e) == 0);
-  }();
-  return on;
+  return BGCN_KNOB_ONCE(sizeof(TX) == 2 ? "BGCN_GEMM_BF16" : "BGCN_GEMM_X6", 1) != 0;
 }
 
 template <class TX>
@@ -1006,8 +1002,7 @@ static int gemm_xwt_t(const TX* X, int64_t ldx, const float* W0, const float* W1
   if (sizeof(TX) == 4 && bf16_mfma_for<TX>() && M >= kX6MinRows && vec && Nc % 128 == 0 && split % 64 == 0 &&
       (reinterpret_cast<uintptr_t>(X) & 15) == 0 && M * ldx * 4 < (int64_t(1) << 32) - 16 &&
       64 * ldw * 4 < (int64_t(1) << 32)) {
-    static const int pipe = [] { const char* e = std::getenv("BGCN_X6_PIPE"); return e ? atoi(e) : 1; }();
-    if (pipe)
+    if (BGCN_KNOB_ONCE("BGCN_X6_PIPE", 1))
       hipLaunchKernelGGL(k_gemm_xwt_x6p, dim3(grid_for(M, 128), unsigned(Nc / 128)), dim3(256), 0, stream,
                          reinterpret_cast<const float*>(X), ldx, W0, W1, ldw, split, Y, ldy, M, K, gate);
     else
@@ -1131,7 +1126,7 @@ static int gemm_tn_t(const float* G, int64_t ldg, const TX* X, int64_t ldx, floa
   const bool xal = (reinterpret_cast<uintptr_t>(X) & (4 * sizeof(TX) - 1)) == 0;
   bool vec = Mc % 4 == 0 && Nc % 4 == 0 && ldg % 4 == 0 && ldx % 4 == 0 && aligned16(G) && xal;
   // fp32 X: the 64 x 64 wave-tile kernel (BGCN_TN_WIDE=0 keeps k_gemm_tn)
-  static const bool wide_on = [] { const char* e = std::getenv("BGCN_TN_WIDE"); return !(e && atoi(e) == 0); }();
+  const bool wide_on = BGCN_KNOB_ONCE("BGCN_TN_WIDE", 1) != 0;
   const bool wide = sizeof(TX) == 4 && vec && wide_on;
   int S = wide ? tn_splits_w(Mc, Nc, K) : tn_splits(Mc, Nc, K);
   int64_t kchunk = (K + S - 1) / S;

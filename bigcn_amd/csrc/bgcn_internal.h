@@ -398,13 +398,11 @@ int bigcn_forward_impl(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, hipS
                        int graph_lane, const HeadArgs* head = nullptr,
                        const Prepared* prep = nullptr, const WeightImages* img = nullptr,
                        bool img_current = false);
-// side_busy: the side lane carries other long work (a next-batch preparation); the dW2
-// chain then stays on the caller's stream
 // head (bgcn_train_step): the classifier head's weight gradients, run as extra blocks of
 // the readout backward
 int bigcn_backward_impl(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, hipStream_t s,
-                        const Prepared* prep = nullptr, bool side_busy = false,
-                        const HeadGradJob* head = nullptr, const WeightImages* img = nullptr,
+                        const Prepared* prep = nullptr, const HeadGradJob* head = nullptr,
+                        const WeightImages* img = nullptr,
                         bool defer_dw1 = false, const TailAdam* adam = nullptr, bool* adam_done = nullptr);
 // the dW1 of a backward run with defer_dw1 (same arguments and buffers)
 int bigcn_backward_dw1(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, hipStream_t s, const Prepared* prep,
@@ -448,7 +446,7 @@ int drop_edges_impl(const int64_t* td, int64_t Etd, int64_t* td_out, int64_t ld_
                     int64_t* counts, int32_t* status, void* ws, size_t ws_bytes, hipStream_t s);
 
 // ---- one training step (bgcn_step.hip)
-size_t train_step_ws_size(int64_t N, int64_t B, int64_t F, int64_t C, int64_t Etd, int64_t Ebu);
+size_t train_step_ws_size(int64_t N, int64_t B, int64_t F, int64_t C);
 int train_step_impl(const bgcn_step_args* a, void* ws, size_t ws_bytes, hipStream_t s);
 // the evaluation loop's reductions after the head (bgcn_head.hip, k_eval_finish)
 int eval_finish_impl(const float* loss_row, const float* logp, const int64_t* y, int64_t B, int32_t C, float* loss,

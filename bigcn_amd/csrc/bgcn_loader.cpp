@@ -362,8 +362,8 @@ int bgcn_loader_create(const bgcn_tree_store* st, const int64_t* indices, int64_
   L->slots.resize(size_t(nslots));
   for (int i = 0; i < nslots; ++i) L->slots[size_t(i)].next = i;
   if (L->pinned && hipGetDevice(&L->device) != hipSuccess) L->pinned = false;
-  if (const char* e = std::getenv("BGCN_LOADER_COPY")) L->sdma = std::strcmp(e, "sdma") == 0;
-  if (const char* e = std::getenv("BGCN_LOADER_COPY_BLOCKS")) L->copy_blocks = std::max(1, std::atoi(e));
+  if (const char* e = knob_text("BGCN_LOADER_COPY")) L->sdma = std::strcmp(e, "sdma") == 0;
+  L->copy_blocks = std::max(1, int(knob("BGCN_LOADER_COPY_BLOCKS", L->copy_blocks)));
   for (size_t k = 0; k < L->slots.size(); ++k) {
     Slot& s = L->slots[k];
     void* p = nullptr;

@@ -68,8 +68,7 @@ AuxState* aux_state(int lane) {
       hipStream_t st;
       // BGCN_SIDE_CU_EVERY=k (A/B knob, read at lane creation): the lane may not use CU i
       // when i % k == k - 1, leaving those CUs to the caller's chain
-      const char* ce = std::getenv("BGCN_SIDE_CU_EVERY");
-      const int every = ce ? atoi(ce) : 0;
+      const int every = int(knob("BGCN_SIDE_CU_EVERY", 0));
       if (every > 1) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return nullptr;
@@ -149,7 +148,7 @@ void timing_end(int cls, hipStream_t s) {
 // BGCN_SERIAL=1 in the environment runs every branch inline (A/B measurements)
 bool serial_branches() {
   static const bool v = [] {
-    const char* e = std::getenv("BGCN_SERIAL");
+    const char* e = knob_text("BGCN_SERIAL");
     return e && e[0] == '1';
   }();
   return v;

@@ -80,11 +80,17 @@ size_t carve_sparse(Carve& c, int64_t N, int64_t B, int64_t F, SparseState* S);
 int sparse_prologue(SparseState& S, const bgcn_bigcn_args* a, int32_t* node_root, hipStream_t s,
                     bool batch_part = true);
 struct Prepared;
-// weight-independent preparation of one batch into p (bgcn_prepare_batch)
-// part 1: node maps, tree items, the ELL of X (the pass over X); part 2: the CSC of X
+// The batch-owned buffers of a prepared batch as sparse state: tree items, the CSC of X and
+// its counting-sort scratch, the spill pool.  The one copy of these fields (the batch
+// preparation and the fused encoder's setup both bind through it); flags / nnz / cols /
+// vals, root_map and bstatus differ between the two and stay with the callers.
+void bind_prepared(const Prepared& p, SparseState& S);
+// weight-independent preparation of one batch into p as separate launches on `s` (a step
+// that prepares its own batch beside K1 on another lane): node maps, tree items, the ELL
+// of X (the pass over X), then the CSC of X
 int sparse_prepare(const Prepared& p, int64_t N, int64_t B, int64_t F, int mode,
                    const int64_t* batch, const int64_t* rootindex, const void* X, int xdt, int64_t ldx,
-                   hipStream_t s, int part = 3, const bgcn_batch* csr = nullptr);
+                   hipStream_t s, const bgcn_batch* csr = nullptr);
 int sparse_conv1_gather(SparseState& S, float* Z1, hipStream_t s);
 int sparse_compact_conv1(SparseState& S, const void* X, int xdt, int64_t ldx, float* Z1,
                          hipStream_t s);

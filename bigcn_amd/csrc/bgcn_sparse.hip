@@ -2061,9 +2061,8 @@ int bwd_tail_launch(BwdTailArgs& a, hipStream_t s, int part) {
   // 0.839 vs 0.850-0.859 ms, weibo_bf16 0.690 vs 0.697, profiles/r02_split_ab.txt);
   // BGCN_DW1_SPLIT=1/4 forces either (read per call: tests compare both)
   // default: the XCD-aware output slices (dw1_sliced_body), BGCN_DW1_SPLIT=0
-  const char* e = std::getenv("BGCN_DW1_SPLIT");
   const bool sparse = a.S.mode != 1;
-  const int split = e ? atoi(e) : 0;
+  const int split = int(knob("BGCN_DW1_SPLIT", 0));
   constexpr int wpb = kTailThreads / 64;   // waves per block
   const int cols1 = split == 4 ? wpb / 4 : wpb;
   a.n_dw1 = !sparse ? 0 : split == 0 ? dw1_sliced_blocks(a.S.F, wpb) : int((a.S.F + cols1 - 1) / cols1);
@@ -2206,17 +2205,21 @@ int sparse_csc(SparseState& S, hipStream_t s) {
 #ifndef BGCN_PREP_LANES_DEFAULT
 #define BGCN_PREP_LANES_DEFAULT 2   // profiles/r03_chain_experiments_late.txt
 #endif
+void bind_prepared(const Prepared& p, SparseState& S) {
+  S.item_tree = p.item_tree; S.tree_item0 = p.tree_item0;
+  S.item_beg = p.item_beg; S.item_end = p.item_end; S.item_root = p.item_root;
+  S.hist = p.hist; S.col_total = p.col_total; S.col_start = p.col_start; S.col_end = p.col_end;
+  S.csc = p.csc;
+  S.ovf_off = p.x_ovf_off; S.ovf = p.x_ovf; S.ovf_cap = p.ovf_cap; S.long_rows = p.x_long;
+}
+
 // the sparse state of a prepared batch's buffers
 static void prepared_state(const Prepared& p, int64_t N, int64_t B, int64_t F, int mode, SparseState& S) {
   S.mode = mode;
   S.N = N; S.F = F; S.B = B;
   S.max_items = int(N / kChunk + B + 1);
   S.flags = p.x_flags; S.nnz = p.x_nnz; S.cols = p.x_cols; S.vals = p.x_vals;
-  S.item_tree = p.item_tree; S.tree_item0 = p.tree_item0;
-  S.item_beg = p.item_beg; S.item_end = p.item_end; S.item_root = p.item_root;
-  S.hist = p.hist; S.col_total = p.col_total; S.col_start = p.col_start; S.col_end = p.col_end;
-  S.csc = p.csc;
-  S.ovf_off = p.x_ovf_off; S.ovf = p.x_ovf; S.ovf_cap = p.ovf_cap; S.long_rows = p.x_long;
+  bind_prepared(p, S);
   S.root_map = p.node_root;
   S.bstatus = p.status;
 }
@@ -2287,9 +2290,7 @@ int prep_pipeline(const Prepared& p, const bgcn_batch* bt, int64_t F, int degree
     }();
     const bool bf = bt->x_dtype == BGCN_DTYPE_BF16;
     a.ncomp = xp ? int(grid_for(N, bf ? 8 : 4)) : 0;
-    int cap = bf ? (compact_by_prefix<bf16_t>() ? ncu : 0) : ncu + ncu / 2;
-    const char* e = std::getenv("BGCN_PREP_BLOCKS");
-    if (e) cap = atoi(e);
+    const int cap = int(knob("BGCN_PREP_BLOCKS", bf ? (compact_by_prefix<bf16_t>() ? ncu : 0) : ncu + ncu / 2));
     if (cap > 0) a.ncomp = std::min(a.ncomp, cap);
     // host-fed compacted rows: 8 rows per block over every row, nothing to pace (nnz x 8 B)
     if (a.xr_ptr && xp) a.ncomp = int(grid_for(N, 8));
@@ -2311,10 +2312,7 @@ int prep_pipeline(const Prepared& p, const bgcn_batch* bt, int64_t F, int degree
   // launches then overlap the X window, where the chain is stalled anyway, instead of the
   // chain's second half: twitter15 0.2691-0.2724 vs 0.2732-0.2749 ms per step over five
   // interleaved rounds, synth1024_bf16 -0.7 %, weibo_bf16 within its noise (+0.5 %)
-  static const int default_lanes = [] {
-    const char* e = std::getenv("BGCN_PREP_LANES");
-    return e ? atoi(e) : BGCN_PREP_LANES_DEFAULT;
-  }();
+  const int default_lanes = int(BGCN_KNOB_ONCE("BGCN_PREP_LANES", BGCN_PREP_LANES_DEFAULT));
   const int lanes = nlanes > 0 ? nlanes : default_lanes;
   if (lanes == 2 && xp) {
     hipStream_t g = s;
@@ -2369,10 +2367,9 @@ int prep_pipeline(const Prepared& p, const bgcn_batch* bt, int64_t F, int degree
 
 int sparse_prepare(const Prepared& p, int64_t N, int64_t B, int64_t F, int mode,
                    const int64_t* batch, const int64_t* rootindex, const void* X, int xdt, int64_t ldx,
-                   hipStream_t s, int part, const bgcn_batch* csr) {
+                   hipStream_t s, const bgcn_batch* csr) {
   SparseState S{};
   prepared_state(p, N, B, F, mode, S);
-  if (!(part & 1)) return mode == 1 ? BGCN_OK : sparse_csc(S, s);
   const int nR = int((N + 255) / 256), nP = int((B + 1 + 255) / 256);
   hipLaunchKernelGGL(k_prologue, dim3(unsigned(nR + nP)), dim3(256), 0, s, S, nullptr, nullptr,
                      nullptr, nullptr, batch, rootindex, p.node_root, p.tree_ptr, 1, 0, nR);
@@ -2391,7 +2388,7 @@ int sparse_prepare(const Prepared& p, int64_t N, int64_t B, int64_t F, int mode,
                        static_cast<const float*>(X), ldx, nullptr);
   timing_end(7, s);
   BGCN_CHECK_LAUNCH();
-  return (part & 2) ? sparse_csc(S, s) : BGCN_OK;
+  return sparse_csc(S, s);
 }
 
 int sparse_conv1_gather(SparseState& S, float* Z1, hipStream_t s) {

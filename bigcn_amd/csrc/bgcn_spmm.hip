@@ -597,8 +597,7 @@ bool spmm_planned(const SpmmBatch& sb, int count) {
     planned = planned && sb.p[k].plan.bnd && sb.p[k].plan.longs && sb.p[k].plan.nlong;
     capmax = sb.p[k].capacity > capmax ? sb.p[k].capacity : capmax;
   }
-  const char* pe = std::getenv("BGCN_SPMM_PLAN");
-  const int plan_env = pe ? atoi(pe) : -1;
+  const int plan_env = int(knob("BGCN_SPMM_PLAN", -1));
   return planned && (plan_env == 1 || (plan_env != 0 && capmax <= kPlanMaxEntries));
 }
 

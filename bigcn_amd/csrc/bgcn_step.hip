@@ -59,6 +59,14 @@ bgcn_graph_view view_of(const bgcn_csr_out& g, int64_t cap) {
   return bgcn_graph_view{g.t_ptr, g.t_row, g.t_col, g.t_w, g.s_ptr, g.s_row, g.s_col, g.s_w, cap};
 }
 
+// the encoder arguments a prepared batch supplies: its graphs, the ELL of X, the tree pointers
+void prepared_args(const Prepared& p, bgcn_bigcn_args* e) {
+  e->td = view_of(p.td, p.td_cap);
+  e->bu = view_of(p.bu, p.bu_cap);
+  e->x_flags = p.x_flags; e->x_nnz = p.x_nnz; e->x_cols = p.x_cols; e->x_vals = p.x_vals;
+  e->tree_ptr = p.tree_ptr;
+}
+
 int check_batch(const bgcn_batch* b) {
   BGCN_CHECK_ARG(b, "null batch");
   BGCN_CHECK_ARG(b->num_nodes > 0 && b->num_graphs > 0, "bad sizes");
@@ -147,12 +155,18 @@ int bigcn_prepared_call(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, hip
   Carve cp(const_cast<void*>(a->prepared), a->prepared_bytes);
   carve_prepared(cp, N, B, F, a->td_num_edges, a->bu_num_edges, &p);
   bgcn_bigcn_args e = *a;
-  e.td = view_of(p.td, p.td_cap);
-  e.bu = view_of(p.bu, p.bu_cap);
-  e.x_flags = p.x_flags; e.x_nnz = p.x_nnz; e.x_cols = p.x_cols; e.x_vals = p.x_vals;
-  e.tree_ptr = p.tree_ptr;
-  if (backward) return bigcn_backward_impl(&e, ws, ws_bytes, s, &p, false);
+  prepared_args(p, &e);
+  if (backward) return bigcn_backward_impl(&e, ws, ws_bytes, s, &p);
   return bigcn_forward_impl(&e, ws, ws_bytes, s, -1, nullptr, &p);
+}
+
+// a batch's prepared buffer as its carved pointers
+static int carve_batch(const bgcn_batch& b, int64_t F, void* buf, size_t bytes, Prepared* p) {
+  BGCN_CHECK_ARG(buf && bytes >= prepared_size(b.num_nodes, b.num_graphs, F, b.td_num_edges, b.bu_num_edges),
+                 "prepared buffer too small");
+  Carve c(buf, bytes);
+  carve_prepared(c, b.num_nodes, b.num_graphs, F, b.td_num_edges, b.bu_num_edges, p);
+  return BGCN_OK;
 }
 
 // gs: stream of the graph build (K1); the caller joins it before the graphs are used
@@ -161,28 +175,20 @@ static int prepare_into(const bgcn_batch* b, int64_t F, int degree_on, int feat_
   BGCN_TRY(check_batch(b));
   BGCN_CHECK_ARG(F > 0 && F % 4 == 0 && b->ldx >= F && b->ldx % 4 == 0, "bad in_feats / ldx");
   const int64_t N = b->num_nodes, B = b->num_graphs;
-  BGCN_CHECK_ARG(buf && bytes >= prepared_size(N, B, F, b->td_num_edges, b->bu_num_edges),
-                 "prepared buffer too small");
   Prepared p;
-  Carve c(buf, bytes);
-  carve_prepared(c, N, B, F, b->td_num_edges, b->bu_num_edges, &p);
+  BGCN_TRY(carve_batch(*b, F, buf, bytes, &p));
   BGCN_TRY(check_feat_input(b, feat_mode, F));
   const int mode = (feat_mode == BGCN_FEAT_DENSE || F > kSparseMaxFeat || N > kSparseMaxN) ? 1 : 0;
   // one stream: the six merged launches (DropEdge, K1, the pass over X and the CSC of X
-  // side by side, bgcn_sparse.hip prep_pipeline).  BGCN_PREP_MERGED=0 (read per call)
-  // selects the separate launches for A/B runs: the pass over X first (beside the
-  // forward, whose gathers are L2-served, it costs the chain less than beside the
-  // backward: 0.322 vs 0.329 ms per step), then DropEdge and K1, then the CSC.
-  const char* me = std::getenv("BGCN_PREP_MERGED");
-  if (s == gs && !(me && atoi(me) == 0)) {
+  // side by side, bgcn_sparse.hip prep_pipeline)
+  if (s == gs) {
     BGCN_TRY(prep_pipeline(p, b, F, degree_on, mode, s, true, lanes));
     if (out) *out = p;
     return BGCN_OK;
   }
+  // the graph build on its own stream (a step that prepares its own batch with nothing to
+  // prefetch): DropEdge and K1 on gs, the pass over X and the CSC as separate launches on s
   BGCN_CHECK_HIP(hipMemsetAsync(p.status, 0, sizeof(int32_t), gs));
-  const bool x_first = s == gs;
-  if (x_first)
-    BGCN_TRY(sparse_prepare(p, N, B, F, mode, b->batch, b->rootindex, b->x, b->x_dtype, b->ldx, s, 1, b));
   const int64_t* td = b->td_edge_index;
   const int64_t* bu = b->bu_edge_index;
   if (b->td_droprate > 0.0 || b->bu_droprate > 0.0) {
@@ -197,14 +203,10 @@ static int prepare_into(const bgcn_batch* b, int64_t F, int degree_on, int feat_
   BGCN_TRY(bgcn_build_graph_pair(td, b->td_num_edges, bu, b->bu_num_edges, N, degree_on, &p.td,
                                  &p.bu, b->batch, p.status, p.gws, p.gws_bytes,
                                  reinterpret_cast<bgcn_stream_t>(gs)));
-  BGCN_TRY(sparse_prepare(p, N, B, F, mode, b->batch, b->rootindex, b->x, b->x_dtype, b->ldx, s,
-                          x_first ? 2 : 3, b));
+  BGCN_TRY(sparse_prepare(p, N, B, F, mode, b->batch, b->rootindex, b->x, b->x_dtype, b->ldx, s, b));
   if (out) *out = p;
   return BGCN_OK;
 }
-
-static int train_step_body(const bgcn_step_args* a, const Prepared& p, StepWs& w, hipStream_t s,
-                           int graph_lane);
 
 // bgcn_step_args.adam as the tail's fused form: its tensors must be exactly the ten step
 // parameters (gradient pointers = the step's grads, torch's sizes), its images the step's
@@ -239,23 +241,43 @@ static bool tail_adam_args(const bgcn_step_args* a, const WeightImages* img, Tai
   return true;
 }
 
-size_t train_step_ws_size(int64_t N, int64_t B, int64_t F, int64_t C, int64_t Etd, int64_t Ebu) {
-  (void)Etd; (void)Ebu;
+size_t train_step_ws_size(int64_t N, int64_t B, int64_t F, int64_t C) {
   Carve c(nullptr, 0);
   return carve_step(c, N, B, F, C, nullptr) + 256;
 }
 
-int train_step_impl(const bgcn_step_args* a, void* ws, size_t ws_bytes, hipStream_t s) {
+// What one step call (bgcn_train_step, bgcn_eval_step, bgcn_train_step_dw1) works on: its
+// carved workspace, its prepared batch, the weight images and the encoder's arguments.
+struct Step {
+  StepWs w;
+  Prepared p;
+  WeightImages im{};
+  const WeightImages* img = nullptr;   // &im, or nullptr without an image buffer
+  bgcn_bigcn_args e;
+  int graph_lane = -1;                 // the lane that builds a just-prepared batch's graphs
+};
+
+// The argument checks the step entry points share, in the one order all of them report:
+// the batch, sizes, feature input, class count, y / loss; then the entry point's own checks
+// (`own`); then the workspace (carved into st->w), the prepared buffers, the next batch and
+// the image buffer.  dw1 (bgcn_train_step_dw1): only the batch, `own` and the workspace.
+typedef int (*StepOwnChecks)(const bgcn_step_args* a);
+static int step_checks(const bgcn_step_args* a, void* ws, size_t ws_bytes, bool dw1, StepOwnChecks own,
+                       Step* st) {
   BGCN_CHECK_ARG(a, "null args");
   BGCN_TRY(check_batch(&a->cur));
   const int64_t N = a->cur.num_nodes, B = a->cur.num_graphs, F = a->in_feats, C = a->num_classes;
-  BGCN_CHECK_ARG(F > 0, "bad sizes");
-  BGCN_TRY(check_feat_input(&a->cur, a->feat_mode, F));
-  BGCN_CHECK_ARG(C >= 1 && C <= kMaxClasses, "num_classes must be in [1, 16]");
-  BGCN_CHECK_ARG(a->y && a->loss, "null pointer");
-  for (int k = 0; k < BGCN_STEP_PARAMS; ++k)
-    BGCN_CHECK_ARG(a->params[k] && a->grads[k], "null parameter / gradient pointer");
-  BGCN_CHECK_ARG(ws && ws_bytes >= train_step_ws_size(N, B, F, C, 0, 0), "workspace too small");
+  if (!dw1) {
+    BGCN_CHECK_ARG(F > 0, "bad sizes");
+    BGCN_TRY(check_feat_input(&a->cur, a->feat_mode, F));
+    BGCN_CHECK_ARG(C >= 1 && C <= kMaxClasses, "num_classes must be in [1, 16]");
+    BGCN_CHECK_ARG(a->y && a->loss, "null pointer");
+  }
+  BGCN_TRY(own(a));
+  BGCN_CHECK_ARG(ws && ws_bytes >= train_step_ws_size(N, B, F, C), "workspace too small");
+  Carve c(ws, ws_bytes);
+  carve_step(c, N, B, F, C, &st->w);
+  if (dw1) return BGCN_OK;
   BGCN_CHECK_ARG(a->prepared, "a prepared buffer is required (bgcn_prepare_workspace_size)");
   if (a->next) {
     BGCN_TRY(check_batch(a->next));
@@ -263,91 +285,109 @@ int train_step_impl(const bgcn_step_args* a, void* ws, size_t ws_bytes, hipStrea
     BGCN_CHECK_ARG(a->next_prepared && a->next_prepared != a->prepared,
                    "next_prepared must be a separate buffer");
   }
-  StepWs w;
-  Carve c(ws, ws_bytes);
-  carve_step(c, N, B, F, C, &w);
   BGCN_CHECK_ARG(c.ok(), "workspace too small");
   BGCN_CHECK_ARG(a->images || !a->images_current, "images_current without an image buffer");
-  Prepared p;
-  int graph_lane = -1;
+  return BGCN_OK;
+}
+
+// The current batch's prepared state (st->p), then the next batch's preparation forked onto
+// the side lane.  timed (the training step): the span classes 8 next-batch preparation,
+// 9 main chain, 10 step.
+static int step_prepare(const bgcn_step_args* a, hipStream_t s, bool timed, Step* st) {
+  const int64_t F = a->in_feats;
   // the previous call's next-batch preparation (this call's batch) must be complete
   // before this stream uses it
   BGCN_TRY(aux_prep_wait(s));
-
-  timing_begin(10, s);   // span classes: 8 next-batch preparation, 9 main chain, 10 step
-  timing_begin(9, s);
+  if (timed) {
+    timing_begin(10, s);
+    timing_begin(9, s);
+  }
   if (!a->prepared_ready) {
     // prepare the current batch first; without a next batch to prefetch, its K1 runs on
     // the side lane beside the pass over X (joined before the first propagate)
     hipStream_t g = s;
     if (!a->next) BGCN_TRY(aux_fork(s, kLaneSide, &g));
     BGCN_TRY(prepare_into(&a->cur, F, a->degree_on, a->feat_mode, a->prepared, a->prepared_bytes, s,
-                          &p, g));
-    if (g != s) graph_lane = kLaneSide;
+                          &st->p, g));
+    if (g != s) st->graph_lane = kLaneSide;
   } else {
-    BGCN_CHECK_ARG(a->prepared_bytes >= prepared_size(N, B, F, a->cur.td_num_edges, a->cur.bu_num_edges),
-                   "prepared buffer too small");
-    Carve cp(a->prepared, a->prepared_bytes);
-    carve_prepared(cp, N, B, F, a->cur.td_num_edges, a->cur.bu_num_edges, &p);
+    BGCN_TRY(carve_batch(a->cur, F, a->prepared, a->prepared_bytes, &st->p));
   }
   if (a->next) {
     // the next batch's weight-independent preparation (K1, ELL and CSC of X: the HBM-
     // bound pass) runs on the side lane beside this step's latency-bound chain
     hipStream_t x;
     BGCN_TRY(aux_fork(s, kLaneSide, &x));
-    timing_begin(8, x);
+    if (timed) timing_begin(8, x);
     BGCN_TRY(prepare_into(a->next, F, a->degree_on, a->feat_mode, a->next_prepared,
                           a->next_prepared_bytes, x, nullptr, x));
-    timing_end(8, x);
+    if (timed) timing_end(8, x);
     // waited for by the next call, not joined by this one: the step's chain ends without a
     // cross-stream wait (chain alone 197 -> 190 us; beside a preparation the join was
     // free, the side lane ends first)
     BGCN_TRY(aux_prep_done(s));
   }
-  BGCN_TRY(train_step_body(a, p, w, s, graph_lane));
-  timing_end(10, s);
   return BGCN_OK;
 }
 
-static int train_step_body(const bgcn_step_args* a, const Prepared& p, StepWs& w, hipStream_t s,
-                           int graph_lane) {
-  const int64_t N = a->cur.num_nodes, B = a->cur.num_graphs, F = a->in_feats, C = a->num_classes;
-  // (*status is cleared by the forward's prologue)
-  bgcn_bigcn_args e{};
-  e.x = a->cur.x; e.x_dtype = a->cur.x_dtype;
-  e.ldx = a->cur.ldx; e.num_nodes = N; e.num_graphs = B; e.in_feats = F; e.hid = H;
-  e.batch = a->cur.batch; e.rootindex = a->cur.rootindex;
-  e.td = view_of(p.td, p.td_cap);
-  e.bu = view_of(p.bu, p.bu_cap);
-  e.td_w1 = a->params[0]; e.td_b1 = a->params[1]; e.td_w2 = a->params[2]; e.td_b2 = a->params[3];
-  e.bu_w1 = a->params[4]; e.bu_b1 = a->params[5]; e.bu_w2 = a->params[6]; e.bu_b2 = a->params[7];
-  e.training = a->training; e.seed = a->seed; e.keep_words = nullptr;
-  e.feat_mode = a->feat_mode;
-  e.x_flags = p.x_flags; e.x_nnz = p.x_nnz; e.x_cols = p.x_cols; e.x_vals = p.x_vals;
-  e.tree_ptr = p.tree_ptr; e.h1 = w.h1; e.h2 = w.h2; e.head_in = w.head; e.dhead_in = w.dhead;
-  e.td_dw1 = a->grads[0]; e.td_db1 = a->grads[1]; e.td_dw2 = a->grads[2]; e.td_db2 = a->grads[3];
-  e.bu_dw1 = a->grads[4]; e.bu_db1 = a->grads[5]; e.bu_dw2 = a->grads[6]; e.bu_db2 = a->grads[7];
-  e.save_for_backward = 1;
-  // forward with the head fused into the readout (fc, log_softmax, NLL row terms, dz,
-  // dhead per tree); the prepared batch's K1 status is folded into *status
-  const HeadArgs hd{a->params[8], a->params[9], a->y, int(C), a->logp, w.dz, w.loss_row, w.dhead,
-                    a->status, p.status, a->feat_mode == BGCN_FEAT_SPARSE ? p.x_flags : nullptr};
-  WeightImages im{};
+// The weight images and the encoder arguments of a step from (bgcn_step_args, st->p, st->w):
+// the only place that fills them (the dW1 call re-derives them from the same inputs).
+static void step_encoder_args(const bgcn_step_args* a, Step* st) {
   if (a->images) {
-    Carve ci(a->images, bgcn_weight_images_size(F));
-    carve_images(ci, F, &im);
+    Carve ci(a->images, bgcn_weight_images_size(a->in_feats));
+    carve_images(ci, a->in_feats, &st->im);
+    st->img = &st->im;
   }
-  const WeightImages* img = a->images ? &im : nullptr;
-  BGCN_TRY(bigcn_forward_impl(&e, w.enc, w.enc_bytes, s, graph_lane, &hd, &p, img, a->images_current != 0));
+  const StepWs& w = st->w;
+  bgcn_bigcn_args* e = &st->e;
+  *e = bgcn_bigcn_args{};
+  e->x = a->cur.x; e->x_dtype = a->cur.x_dtype;
+  e->ldx = a->cur.ldx; e->num_nodes = a->cur.num_nodes; e->num_graphs = a->cur.num_graphs;
+  e->in_feats = a->in_feats; e->hid = H;
+  e->batch = a->cur.batch; e->rootindex = a->cur.rootindex;
+  prepared_args(st->p, e);
+  e->td_w1 = a->params[0]; e->td_b1 = a->params[1]; e->td_w2 = a->params[2]; e->td_b2 = a->params[3];
+  e->bu_w1 = a->params[4]; e->bu_b1 = a->params[5]; e->bu_w2 = a->params[6]; e->bu_b2 = a->params[7];
+  e->training = a->training; e->seed = a->seed; e->keep_words = nullptr;
+  e->feat_mode = a->feat_mode;
+  e->h1 = w.h1; e->h2 = w.h2; e->head_in = w.head; e->dhead_in = w.dhead;
+  e->td_dw1 = a->grads[0]; e->td_db1 = a->grads[1]; e->td_dw2 = a->grads[2]; e->td_db2 = a->grads[3];
+  e->bu_dw1 = a->grads[4]; e->bu_db1 = a->grads[5]; e->bu_dw2 = a->grads[6]; e->bu_db2 = a->grads[7];
+  e->save_for_backward = 1;
+}
+
+// the head fused into the readout (fc, log_softmax, NLL row terms, dz, dhead per tree); the
+// prepared batch's K1 status is folded into *status
+static HeadArgs step_head(const bgcn_step_args* a, const Step& st, float* logp) {
+  return HeadArgs{a->params[8], a->params[9], a->y, int(a->num_classes), logp, st.w.dz, st.w.loss_row,
+                  st.w.dhead, a->status, st.p.status,
+                  a->feat_mode == BGCN_FEAT_SPARSE ? st.p.x_flags : nullptr};
+}
+
+int train_step_impl(const bgcn_step_args* a, void* ws, size_t ws_bytes, hipStream_t s) {
+  Step st;
+  BGCN_TRY(step_checks(a, ws, ws_bytes, false, [](const bgcn_step_args* a) -> int {
+    for (int k = 0; k < BGCN_STEP_PARAMS; ++k)
+      BGCN_CHECK_ARG(a->params[k] && a->grads[k], "null parameter / gradient pointer");
+    return BGCN_OK;
+  }, &st));
+  BGCN_TRY(step_prepare(a, s, true, &st));
+  step_encoder_args(a, &st);
+  const StepWs& w = st.w;
+  const int64_t B = a->cur.num_graphs, C = a->num_classes;
+  // (*status is cleared by the forward's prologue)
+  const HeadArgs hd = step_head(a, st, a->logp);
+  BGCN_TRY(bigcn_forward_impl(&st.e, w.enc, w.enc_bytes, s, st.graph_lane, &hd, &st.p, st.img,
+                              a->images_current != 0));
   // fc weight/bias gradients, the loss mean and the validity flag: extra blocks of the
   // readout backward (joins the side lane at its end; with a next-batch preparation on
   // the side lane the dW2 chain stays on this stream, which balances the two)
   const HeadGradJob hj{w.head, w.dz, B, int(C), w.loss_row, a->grads[8], a->grads[9], a->loss,
                        a->status, a->status_flag, a->status_seen};
   TailAdam ta;
-  const bool fuse = a->adam && !a->defer_dw1 && tail_adam_args(a, img, ta);
+  const bool fuse = a->adam && !a->defer_dw1 && tail_adam_args(a, st.img, ta);
   bool done = false;
-  BGCN_TRY(bigcn_backward_impl(&e, w.enc, w.enc_bytes, s, &p, a->next != nullptr, &hj, img, a->defer_dw1 != 0,
+  BGCN_TRY(bigcn_backward_impl(&st.e, w.enc, w.enc_bytes, s, &st.p, &hj, st.img, a->defer_dw1 != 0,
                                fuse ? &ta : nullptr, &done));
   // the optimiser step the tail did not take: its own launch (same bits)
   if (a->adam && !done) {
@@ -356,6 +396,7 @@ static int train_step_body(const bgcn_step_args* a, const Prepared& p, StepWs& w
     const int rc = bgcn_adam_step(a->adam, reinterpret_cast<bgcn_stream_t>(s));
     if (rc != BGCN_OK) return rc;
   }
+  timing_end(10, s);
   return BGCN_OK;
 }
 
@@ -367,119 +408,39 @@ static int train_step_body(const bgcn_step_args* a, const Prepared& p, StepWs& w
 // sync; the next batch's preparation rides on the side lane as in the training step.
 int eval_step_impl(const bgcn_step_args* a, int32_t* correct, int64_t* pred, void* ws, size_t ws_bytes,
                    hipStream_t s) {
-  BGCN_CHECK_ARG(a, "null args");
-  BGCN_TRY(check_batch(&a->cur));
-  const int64_t N = a->cur.num_nodes, B = a->cur.num_graphs, F = a->in_feats, C = a->num_classes;
-  BGCN_CHECK_ARG(F > 0, "bad sizes");
-  BGCN_TRY(check_feat_input(&a->cur, a->feat_mode, F));
-  BGCN_CHECK_ARG(C >= 1 && C <= kMaxClasses, "num_classes must be in [1, 16]");
-  BGCN_CHECK_ARG(a->y && a->loss, "null pointer");
-  BGCN_CHECK_ARG(a->training == 0, "the evaluation step runs in eval mode (training = 0)");
-  BGCN_CHECK_ARG(a->cur.td_droprate == 0.0 && a->cur.bu_droprate == 0.0,
-                 "the evaluation step drops no edges (the test set's BiGraphDataset)");
-  for (int k = 0; k < BGCN_STEP_PARAMS; ++k) BGCN_CHECK_ARG(a->params[k], "null parameter pointer");
-  BGCN_CHECK_ARG(ws && ws_bytes >= train_step_ws_size(N, B, F, C, 0, 0), "workspace too small");
-  BGCN_CHECK_ARG(a->prepared, "a prepared buffer is required (bgcn_prepare_workspace_size)");
-  if (a->next) {
-    BGCN_TRY(check_batch(a->next));
-    BGCN_TRY(check_feat_input(a->next, a->feat_mode, F));
-    BGCN_CHECK_ARG(a->next_prepared && a->next_prepared != a->prepared, "next_prepared must be a separate buffer");
-  }
-  StepWs w;
-  Carve c(ws, ws_bytes);
-  carve_step(c, N, B, F, C, &w);
-  BGCN_CHECK_ARG(c.ok(), "workspace too small");
-  BGCN_CHECK_ARG(a->images || !a->images_current, "images_current without an image buffer");
-  Prepared p;
-  int graph_lane = -1;
-  BGCN_TRY(aux_prep_wait(s));
-  if (!a->prepared_ready) {
-    hipStream_t g = s;
-    if (!a->next) BGCN_TRY(aux_fork(s, kLaneSide, &g));
-    BGCN_TRY(prepare_into(&a->cur, F, a->degree_on, a->feat_mode, a->prepared, a->prepared_bytes, s, &p, g));
-    if (g != s) graph_lane = kLaneSide;
-  } else {
-    BGCN_CHECK_ARG(a->prepared_bytes >= prepared_size(N, B, F, a->cur.td_num_edges, a->cur.bu_num_edges),
-                   "prepared buffer too small");
-    Carve cp(a->prepared, a->prepared_bytes);
-    carve_prepared(cp, N, B, F, a->cur.td_num_edges, a->cur.bu_num_edges, &p);
-  }
-  if (a->next) {
-    hipStream_t x;
-    BGCN_TRY(aux_fork(s, kLaneSide, &x));
-    BGCN_TRY(prepare_into(a->next, F, a->degree_on, a->feat_mode, a->next_prepared, a->next_prepared_bytes, x,
-                          nullptr, x));
-    BGCN_TRY(aux_prep_done(s));
-  }
-  bgcn_bigcn_args e{};
-  e.x = a->cur.x; e.x_dtype = a->cur.x_dtype;
-  e.ldx = a->cur.ldx; e.num_nodes = N; e.num_graphs = B; e.in_feats = F; e.hid = H;
-  e.batch = a->cur.batch; e.rootindex = a->cur.rootindex;
-  e.td = view_of(p.td, p.td_cap);
-  e.bu = view_of(p.bu, p.bu_cap);
-  e.td_w1 = a->params[0]; e.td_b1 = a->params[1]; e.td_w2 = a->params[2]; e.td_b2 = a->params[3];
-  e.bu_w1 = a->params[4]; e.bu_b1 = a->params[5]; e.bu_w2 = a->params[6]; e.bu_b2 = a->params[7];
-  e.training = 0; e.seed = 0; e.keep_words = nullptr;
-  e.feat_mode = a->feat_mode;
-  e.x_flags = p.x_flags; e.x_nnz = p.x_nnz; e.x_cols = p.x_cols; e.x_vals = p.x_vals;
-  e.tree_ptr = p.tree_ptr; e.h1 = w.h1; e.h2 = w.h2; e.head_in = w.head; e.dhead_in = w.dhead;
-  e.save_for_backward = 0;
+  Step st;
+  BGCN_TRY(step_checks(a, ws, ws_bytes, false, [](const bgcn_step_args* a) -> int {
+    BGCN_CHECK_ARG(a->training == 0, "the evaluation step runs in eval mode (training = 0)");
+    BGCN_CHECK_ARG(a->cur.td_droprate == 0.0 && a->cur.bu_droprate == 0.0,
+                   "the evaluation step drops no edges (the test set's BiGraphDataset)");
+    for (int k = 0; k < BGCN_STEP_PARAMS; ++k) BGCN_CHECK_ARG(a->params[k], "null parameter pointer");
+    return BGCN_OK;
+  }, &st));
+  BGCN_TRY(step_prepare(a, s, false, &st));
+  step_encoder_args(a, &st);
+  // eval mode: no dropout draw, nothing saved for a backward, no gradient buffers
+  bgcn_bigcn_args& e = st.e;
+  e.training = 0; e.seed = 0; e.save_for_backward = 0;
+  e.td_dw1 = e.td_db1 = e.td_dw2 = e.td_db2 = e.bu_dw1 = e.bu_db1 = e.bu_dw2 = e.bu_db2 = nullptr;
+  const StepWs& w = st.w;
   float* logp = a->logp ? a->logp : w.logp;
-  const HeadArgs hd{a->params[8], a->params[9], a->y, int(C), logp, w.dz, w.loss_row, w.dhead,
-                    a->status, p.status, a->feat_mode == BGCN_FEAT_SPARSE ? p.x_flags : nullptr};
-  WeightImages im{};
-  if (a->images) {
-    Carve ci(a->images, bgcn_weight_images_size(F));
-    carve_images(ci, F, &im);
-  }
-  BGCN_TRY(bigcn_forward_impl(&e, w.enc, w.enc_bytes, s, graph_lane, &hd, &p, a->images ? &im : nullptr,
+  const HeadArgs hd = step_head(a, st, logp);
+  BGCN_TRY(bigcn_forward_impl(&e, w.enc, w.enc_bytes, s, st.graph_lane, &hd, &st.p, st.img,
                               a->images_current != 0));
-  return eval_finish_impl(w.loss_row, logp, a->y, B, int(C), a->loss, correct, pred, a->status, a->status_seen, s);
-}
-
-// the encoder arguments of a step (the dW1 call re-derives them from the same inputs)
-static void step_encoder_args(const bgcn_step_args* a, const Prepared& p, const StepWs& w, bgcn_bigcn_args* e) {
-  *e = bgcn_bigcn_args{};
-  e->x = a->cur.x; e->x_dtype = a->cur.x_dtype;
-  e->ldx = a->cur.ldx; e->num_nodes = a->cur.num_nodes; e->num_graphs = a->cur.num_graphs;
-  e->in_feats = a->in_feats; e->hid = H;
-  e->batch = a->cur.batch; e->rootindex = a->cur.rootindex;
-  e->td = view_of(p.td, p.td_cap);
-  e->bu = view_of(p.bu, p.bu_cap);
-  e->td_w1 = a->params[0]; e->td_b1 = a->params[1]; e->td_w2 = a->params[2]; e->td_b2 = a->params[3];
-  e->bu_w1 = a->params[4]; e->bu_b1 = a->params[5]; e->bu_w2 = a->params[6]; e->bu_b2 = a->params[7];
-  e->training = a->training; e->seed = a->seed; e->keep_words = nullptr;
-  e->feat_mode = a->feat_mode;
-  e->x_flags = p.x_flags; e->x_nnz = p.x_nnz; e->x_cols = p.x_cols; e->x_vals = p.x_vals;
-  e->tree_ptr = p.tree_ptr; e->h1 = w.h1; e->h2 = w.h2; e->head_in = w.head; e->dhead_in = w.dhead;
-  e->td_dw1 = a->grads[0]; e->td_db1 = a->grads[1]; e->td_dw2 = a->grads[2]; e->td_db2 = a->grads[3];
-  e->bu_dw1 = a->grads[4]; e->bu_db1 = a->grads[5]; e->bu_dw2 = a->grads[6]; e->bu_db2 = a->grads[7];
-  e->save_for_backward = 1;
+  return eval_finish_impl(w.loss_row, logp, a->y, a->cur.num_graphs, int(a->num_classes), a->loss, correct, pred,
+                          a->status, a->status_seen, s);
 }
 
 int train_step_dw1_impl(const bgcn_step_args* a, void* ws, size_t ws_bytes, hipStream_t s) {
-  BGCN_CHECK_ARG(a, "null args");
-  BGCN_TRY(check_batch(&a->cur));
-  const int64_t N = a->cur.num_nodes, B = a->cur.num_graphs, F = a->in_feats, C = a->num_classes;
-  BGCN_CHECK_ARG(a->defer_dw1, "bgcn_train_step_dw1 follows a step run with defer_dw1 = 1");
-  BGCN_CHECK_ARG(a->grads[0] && a->grads[4], "null gradient pointer");
-  BGCN_CHECK_ARG(ws && ws_bytes >= train_step_ws_size(N, B, F, C, 0, 0), "workspace too small");
-  BGCN_CHECK_ARG(a->prepared && a->prepared_bytes >= prepared_size(N, B, F, a->cur.td_num_edges, a->cur.bu_num_edges),
-                 "prepared buffer too small");
-  StepWs w;
-  Carve c(ws, ws_bytes);
-  carve_step(c, N, B, F, C, &w);
-  Prepared p;
-  Carve cp(a->prepared, a->prepared_bytes);
-  carve_prepared(cp, N, B, F, a->cur.td_num_edges, a->cur.bu_num_edges, &p);
-  bgcn_bigcn_args e;
-  step_encoder_args(a, p, w, &e);
-  WeightImages im{};
-  if (a->images) {
-    Carve ci(a->images, bgcn_weight_images_size(F));
-    carve_images(ci, F, &im);
-  }
-  return bigcn_backward_dw1(&e, w.enc, w.enc_bytes, s, &p, a->images ? &im : nullptr);
+  Step st;
+  BGCN_TRY(step_checks(a, ws, ws_bytes, true, [](const bgcn_step_args* a) -> int {
+    BGCN_CHECK_ARG(a->defer_dw1, "bgcn_train_step_dw1 follows a step run with defer_dw1 = 1");
+    BGCN_CHECK_ARG(a->grads[0] && a->grads[4], "null gradient pointer");
+    return BGCN_OK;
+  }, &st));
+  BGCN_TRY(carve_batch(a->cur, a->in_feats, a->prepared, a->prepared_bytes, &st.p));
+  step_encoder_args(a, &st);
+  return bigcn_backward_dw1(&st.e, st.w.enc, st.w.enc_bytes, s, &st.p, st.img);
 }
 
 }  // namespace bgcn
@@ -502,9 +463,9 @@ extern "C" int bgcn_prepare_batch(const bgcn_batch* batch, int64_t in_feats, int
 
 extern "C" size_t bgcn_train_step_workspace_size(int64_t num_nodes, int64_t num_graphs,
                                                  int64_t in_feats, int64_t num_classes,
-                                                 int64_t td_num_edges, int64_t bu_num_edges) {
-  return bgcn::train_step_ws_size(num_nodes, num_graphs, in_feats, num_classes, td_num_edges,
-                                  bu_num_edges);
+                                                 int64_t /*td_num_edges*/, int64_t /*bu_num_edges*/) {
+  // (the edge counts size the prepared buffer, bgcn_prepare_workspace_size, not this one)
+  return bgcn::train_step_ws_size(num_nodes, num_graphs, in_feats, num_classes);
 }
 
 extern "C" int bgcn_train_step_saved(void* workspace, size_t workspace_bytes, int64_t num_nodes,
@@ -513,7 +474,7 @@ extern "C" int bgcn_train_step_saved(void* workspace, size_t workspace_bytes, in
   using namespace bgcn;
   BGCN_CHECK_ARG(num_nodes > 0 && num_graphs > 0 && in_feats > 0 && num_classes >= 1, "bad sizes");
   BGCN_CHECK_ARG(workspace && h1 && h2 &&
-                     workspace_bytes >= train_step_ws_size(num_nodes, num_graphs, in_feats, num_classes, 0, 0),
+                     workspace_bytes >= train_step_ws_size(num_nodes, num_graphs, in_feats, num_classes),
                  "workspace too small");
   StepWs w;
   Carve c(workspace, workspace_bytes);

@@ -58,6 +58,101 @@ def test_invalid_arguments_fail_before_any_device_work():
     assert lib.bgcn_adam_step(None, None) == -1
 
 
+def test_step_entry_points_report_their_argument_checks():
+    """bgcn_train_step / bgcn_eval_step / bgcn_train_step_dw1 reject a malformed call with the
+    message of the first check it fails, before any HIP call: the pointer fields hold fake
+    16-byte-aligned addresses that are never dereferenced."""
+    from bigcn_amd import _lib
+    lib = _lib.load_library()
+    fake = 0x10000
+    N, B, F, C, E = 43, 3, 64, 4, 40
+
+    def batch():
+        b = _lib.BatchDesc()
+        b.x, b.ldx, b.num_nodes, b.num_graphs = fake, F, N, B
+        b.batch, b.rootindex = fake + 0x100, fake + 0x200
+        b.td_edge_index, b.td_num_edges, b.bu_edge_index, b.bu_num_edges = fake + 0x300, E, fake + 0x400, E
+        b.x_dtype = _lib.BGCN_DTYPE_F32
+        return b
+
+    def plausible():
+        a = _lib.StepArgs()
+        a.cur = batch()
+        a.in_feats, a.num_classes, a.y, a.loss = F, C, fake + 0x500, fake + 0x600
+        for k in range(_lib.BGCN_STEP_PARAMS):
+            a.params[k] = fake + 0x1000 + 0x100 * k
+            a.grads[k] = fake + 0x2000 + 0x100 * k
+        a.prepared, a.prepared_bytes, a.prepared_ready = fake + 0x10000, 1 << 30, 1
+        return a
+
+    def train(a, ws=None, ws_bytes=0):
+        return lib.bgcn_train_step(ctypes.addressof(a), ws, ws_bytes, None)
+
+    def evaluate(a, ws=None, ws_bytes=0):
+        return lib.bgcn_eval_step(ctypes.addressof(a), None, None, ws, ws_bytes, None)
+
+    def dw1(a, ws=None, ws_bytes=0):
+        return lib.bgcn_train_step_dw1(ctypes.addressof(a), ws, ws_bytes, None)
+
+    def rejected(rc, text):
+        assert rc == -1
+        assert text in lib.bgcn_last_error(), lib.bgcn_last_error()
+
+    for call in (train, evaluate, dw1):
+        rejected(call(_lib.StepArgs()), b"bad sizes")
+    # a plausible batch without a workspace
+    rejected(train(plausible()), b"workspace too small")
+    rejected(evaluate(plausible()), b"workspace too small")
+    a = plausible()
+    a.defer_dw1 = 1
+    rejected(dw1(a), b"workspace too small")
+    # each entry point's own checks come before the workspace's
+    a = plausible()
+    a.training = 1
+    rejected(evaluate(a), b"eval mode")
+    a = plausible()
+    a.cur.td_droprate = 0.25
+    rejected(evaluate(a), b"drops no edges")
+    rejected(dw1(plausible()), b"defer_dw1")
+    a = plausible()
+    a.params[3] = None
+    rejected(train(a), b"null parameter / gradient pointer")
+    rejected(evaluate(a), b"null parameter pointer")
+    a = plausible()
+    a.grads[3] = None
+    rejected(train(a), b"null parameter / gradient pointer")
+    rejected(evaluate(a), b"workspace too small")     # the evaluation step takes no gradients
+    a.defer_dw1 = 1
+    rejected(dw1(a), b"workspace too small")          # dW1 needs only its two
+    a.grads[4] = None
+    rejected(dw1(a), b"null gradient pointer")
+    # the class count is checked by the two full steps, not by the dW1 call
+    a = plausible()
+    a.num_classes, a.defer_dw1 = 17, 1
+    rejected(train(a), b"num_classes must be in [1, 16]")
+    rejected(evaluate(a), b"num_classes must be in [1, 16]")
+    rejected(dw1(a), b"workspace too small")
+    # after the workspace: the prepared buffers
+    ws_bytes = lib.bgcn_train_step_workspace_size(N, B, F, C, E, E)
+    ws = fake + 0x100000
+    a = plausible()
+    nxt = batch()
+    a.next = ctypes.pointer(nxt)
+    a.next_prepared, a.next_prepared_bytes = a.prepared, a.prepared_bytes
+    rejected(train(a, ws, ws_bytes), b"separate buffer")
+    rejected(evaluate(a, ws, ws_bytes), b"separate buffer")
+    a = plausible()
+    a.prepared = None
+    rejected(train(a, ws, ws_bytes), b"a prepared buffer is required")
+    rejected(evaluate(a, ws, ws_bytes), b"a prepared buffer is required")
+    a.defer_dw1 = 1
+    rejected(dw1(a, ws, ws_bytes), b"prepared buffer too small")
+    a = plausible()
+    a.images_current = 1
+    rejected(train(a, ws, ws_bytes), b"images_current without an image buffer")
+    rejected(evaluate(a, ws, ws_bytes), b"images_current without an image buffer")
+
+
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="gcc not available")
 def test_ctypes_struct_layout_matches_header(tmp_path):
     from bigcn_amd import _lib

@@ -109,6 +109,42 @@ def test_eval_step_full_size_vs_oracle(workload):
     assert torch.equal(loss, loss0) and torch.equal(correct, correct0)
 
 
+def test_eval_step_preparing_its_own_batch_matches_a_batch_prepared_ahead():
+    """An evaluation step that prepares its batch inside the call (prepared_ready = 0, no next
+    batch: K1 on the side lane beside the pass over X and the CSC of X as separate launches)
+    gives the bits of the same batch evaluated from a buffer bgcn_prepare_batch filled ahead
+    (the merged launches).  Trees of 1, 2 and 40 nodes, F = 64, one row of 33 non-zeros (one
+    entry in the spill pool).  Both preparations build the same lists in the same order, so
+    loss, log-probabilities and predictions are compared bit for bit."""
+    from bigcn_amd import FusedTrainStep
+    from bigcn_amd.data import synth_batch
+    from bigcn_amd.ops import prepare_batch
+    rng = np.random.default_rng(7)
+    b = synth_batch(rng, [1, 2, 40], 64, 4, 0.0, 0.0, device=DEV)
+    b.x[17].zero_()
+    b.x[17, 5:38] = 1.0
+    assert int((b.x[17] != 0).sum()) == 33
+    m = _model(O.make_params(64, 64, 64, 4, seed=33), 64)
+    m.eval()
+    st = FusedTrainStep(m)
+    logp = torch.empty(3, 4, device=DEV)
+    loss, correct, pred = st.evaluate(b, logp=logp, pred=True)
+    assert st._args.prepared_ready == 0 and not st._args.next
+    ahead = prepare_batch(b, m.degree_on, "auto")
+    d, keep = st._desc(b, drop=False)
+    st._pending = (b, ahead.buf, (False, False), keep, d)     # as a previous call's prefetch leaves it
+    logp1 = torch.empty(3, 4, device=DEV)
+    loss1, correct1, pred1 = st.evaluate(b, logp=logp1, pred=True)
+    assert st._args.prepared_ready == 1 and st._args.prepared == ahead.buf.data_ptr()
+    torch.cuda.synchronize()
+    st.check_status()
+    assert torch.equal(loss, loss1) and torch.equal(logp, logp1)
+    assert torch.equal(pred, pred1) and torch.equal(correct, correct1)
+    rloss, rlogp = _oracle_eval(b, O.make_params(64, 64, 64, 4, seed=33))
+    close(logp, rlogp, what="logp")
+    close(loss, rloss, what="loss")
+
+
 def test_eval_step_matches_per_op_model_and_training_loss():
     """The evaluation step's log-probabilities equal the drop-in modules' model(data) in
     eval mode (the same kernels, 1e-5), and with dropout off its loss equals the training
