@@ -44,6 +44,7 @@ import numpy as np
 import torch
 
 from .data import SPARSE_CAP, VOCAB, synth_parents, synth_tree_sizes
+from .ops import x_dtype_code
 
 _ALIGN = 256
 SPILL_PER_ROW = 32   # = BGCN_SPARSE_SPILL_PER_ROW
@@ -623,9 +624,8 @@ class PackedBatch:
             x = torch.empty(N, F, dtype=self.x_dtype, device=self.buf.device)
             st = torch.zeros(1, dtype=torch.int32, device=self.buf.device)
             _lib.check(_lib.lib().bgcn_csr_to_dense(self._ptr["x_row_ptr"], self._ptr["x_col"], self._ptr["x_val"],
-                                                    N, F, x.data_ptr(), F,
-                                                    _lib.BGCN_DTYPE_BF16 if self.x_dtype == torch.bfloat16
-                                                    else _lib.BGCN_DTYPE_F32, st.data_ptr(), _lib.stream_handle()))
+                                                    N, F, x.data_ptr(), F, x_dtype_code(x), st.data_ptr(),
+                                                    _lib.stream_handle()))
             if int(st.item()) & 1:   # (one host read, on the first access only)
                 raise IndexError("a feature column outside [0, in_feats) in the batch's x_col")
             self._x = x
@@ -633,14 +633,13 @@ class PackedBatch:
 
     def fill_desc(self, d) -> None:
         """bgcn_batch fields of this batch (features compacted: x = NULL)."""
-        from . import _lib
         p, m = self._ptr, self.meta
         d.x, d.ldx = None, self.in_feats
         d.num_nodes, d.num_graphs = m["N"], m["B"]
         d.batch, d.rootindex = p["batch"], p["rootindex"]
         d.td_edge_index, d.td_num_edges = p["edge_index"], m["Etd"]
         d.bu_edge_index, d.bu_num_edges = p["BU_edge_index"], m["Ebu"]
-        d.x_dtype = _lib.BGCN_DTYPE_BF16 if self.x_dtype == torch.bfloat16 else _lib.BGCN_DTYPE_F32
+        d.x_dtype = x_dtype_code(self.x_dtype)
         d.x_row_ptr, d.x_col, d.x_val = p["x_row_ptr"], p["x_col"], p["x_val"]
 
     def keys(self):

@@ -25,7 +25,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import BiGCNArgs, GraphView, check, ptr, stream_handle, workspace
+from ._lib import BatchDesc, BiGCNArgs, GraphView, check, ptr, stream_handle, workspace
 
 HID = 64
 
@@ -140,12 +140,17 @@ def degree_code(degree_on: str) -> int:
     raise ValueError(f"degree_on must be 'col' or 'row', got {degree_on!r}")
 
 
+def _i64c(t: torch.Tensor) -> torch.Tensor:
+    """An index tensor as the kernels read it: int64 and contiguous, else converted."""
+    if t.dtype == torch.int64 and t.is_contiguous():
+        return t
+    return t.to(torch.int64).contiguous()
+
+
 def _check_ei(edge_index: torch.Tensor) -> torch.Tensor:
     if edge_index.dim() != 2 or edge_index.size(0) != 2:
         raise ValueError("edge_index must be [2, E]")
-    if edge_index.dtype == torch.int64 and edge_index.is_contiguous():
-        return edge_index
-    return edge_index.to(torch.int64).contiguous()
+    return _i64c(edge_index)
 
 
 def build_graph_pair(td_edge_index: torch.Tensor, bu_edge_index: torch.Tensor, num_nodes: int,
@@ -638,15 +643,20 @@ def _feat_code(feat_mode) -> int:
     return feat_mode if isinstance(feat_mode, int) else _FEAT_MODES[feat_mode]
 
 
+def check_param_shapes(params, F: int) -> None:
+    """The 8 encoder parameters (reference order) have the shapes of in_feats = F."""
+    want = [(HID, F), (HID,), (HID, HID + F), (HID,)] * 2
+    for p, shp in zip(params, want):
+        if tuple(p.shape) != shp:
+            raise ValueError(f"parameter of shape {tuple(p.shape)}, expected {shp} for in_feats={F}")
+
+
 def check_encoder_shapes(x: torch.Tensor, batch: torch.Tensor, rootindex: torch.Tensor, params) -> None:
     """Host-side shape contract of the fused encoder (the kernels trust it)."""
     if x.dim() != 2:
         raise ValueError("x must be [N, F]")
     N, F = x.shape
-    want = [(HID, F), (HID,), (HID, HID + F), (HID,)] * 2
-    for p, shp in zip(params, want):
-        if tuple(p.shape) != shp:
-            raise ValueError(f"parameter of shape {tuple(p.shape)}, expected {shp} for in_feats={F}")
+    check_param_shapes(params, F)
     if batch.numel() != N:
         raise ValueError("batch must have one entry per node")
     if rootindex.dim() != 1:
@@ -662,25 +672,53 @@ def features(x: torch.Tensor) -> torch.Tensor:
     return x.contiguous()
 
 
-def x_dtype_code(x: torch.Tensor) -> int:
-    return _lib.BGCN_DTYPE_BF16 if x.dtype == torch.bfloat16 else _lib.BGCN_DTYPE_F32
+def x_dtype_code(x) -> int:
+    """BGCN_DTYPE_* of a feature tensor (or of its dtype)."""
+    dtype = x if isinstance(x, torch.dtype) else x.dtype
+    return _lib.BGCN_DTYPE_BF16 if dtype == torch.bfloat16 else _lib.BGCN_DTYPE_F32
+
+
+def dense_batch_desc(data):
+    """``(bgcn_batch, tensors)`` of a collated batch with a dense ``x``: the descriptor's
+    features, sizes, index vectors and edge lists (no DropEdge), and the tensors its
+    pointers point into - ``(x, td_ei, bu_ei, batch, rootindex)`` as the kernels read them
+    (:func:`features`, int64, contiguous), to be kept alive while the descriptor is used."""
+    x = features(data.x)
+    td_ei, bu_ei = _check_ei(data.edge_index), _check_ei(data.BU_edge_index)
+    batch, root = _i64c(data.batch), _i64c(data.rootindex)
+    d = BatchDesc()
+    d.x, d.ldx, d.num_nodes, d.num_graphs = ptr(x), x.stride(0), x.size(0), root.numel()
+    d.x_dtype = x_dtype_code(x)
+    d.batch, d.rootindex = ptr(batch), ptr(root)
+    d.td_edge_index, d.td_num_edges = ptr(td_ei), td_ei.size(1)
+    d.bu_edge_index, d.bu_num_edges = ptr(bu_ei), bu_ei.size(1)
+    return d, (x, td_ei, bu_ei, batch, root)
 
 
 _GRAD_ORDER = tuple(n.replace("_w", "_dw").replace("_b", "_db") for n in _PARAM_ORDER)
 
 
-def _fill_args(a: BiGCNArgs, x, batch, rootindex, td, bu, B, training, seed, keep, feat_mode, xs, params):
+def _fill_args(a: BiGCNArgs, x, batch, rootindex, graphs, B, training, seed, keep, feat_mode, xs, params):
+    """``graphs``: the batch's ``(td, bu)`` :class:`Graph` pair, or its :class:`PreparedBatch`
+    (bgcn_bigcn_args.prepared: graphs, tree pointers and the ELL of X come from its buffer)."""
     N, F = x.shape
     a.x, a.ldx, a.num_nodes, a.num_graphs, a.in_feats, a.hid = x.data_ptr(), x.stride(0), N, B, F, HID
     a.x_dtype = x_dtype_code(x)
     a.batch, a.rootindex = batch.data_ptr(), rootindex.data_ptr()
-    a.td, a.bu = td.view(), bu.view()
+    if isinstance(graphs, PreparedBatch):
+        a.prepared, a.prepared_bytes = graphs.buf.data_ptr(), graphs.buf.numel()
+        a.td_num_edges, a.bu_num_edges = graphs.td_num_edges, graphs.bu_num_edges
+    else:
+        a.td, a.bu = graphs[0].view(), graphs[1].view()
     a.td_w1, a.td_b1, a.td_w2, a.td_b2, a.bu_w1, a.bu_b1, a.bu_w2, a.bu_b2 = (p.data_ptr() for p in params)
     a.training, a.seed = int(bool(training)), int(seed) & (2**64 - 1)
     a.keep_words = ptr(keep)
     a.feat_mode = feat_mode
     if xs is not None:
         a.x_flags, a.x_nnz, a.x_cols, a.x_vals = (t.data_ptr() for t in xs)
+
+
+_ENC_SAVED = 11   # tensors of _encoder_forward's `saved` before the parameters
 
 
 def _encoder_forward(ctx, x, batch, rootindex, td: Graph, bu: Graph, B, training, seed, keep_words,
@@ -693,73 +731,40 @@ def _encoder_forward(ctx, x, batch, rootindex, td: Graph, bu: Graph, B, training
     N, F = x.shape
     dev = x.device
     L = _lib.lib()
+    xs = tree_ptr = None
     if prep is not None:
-        return _encoder_forward_prepared(ctx, x, batch, rootindex, B, training, seed, keep_words, feat_mode,
-                                         params, stream, prep)
-    xs = None
-    if feat_mode != _lib.BGCN_FEAT_DENSE:
-        cap = _lib.BGCN_SPARSE_CAP
-        xs = (torch.empty(8, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
-              torch.empty(N * cap, dtype=torch.int32, device=dev),
-              torch.empty(N * cap, dtype=torch.float32, device=dev))
+        prep.check_matches(x, batch, rootindex, B, feat_mode)
+    else:
+        if feat_mode != _lib.BGCN_FEAT_DENSE:
+            cap = _lib.BGCN_SPARSE_CAP
+            xs = (torch.empty(8, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev),
+                  torch.empty(N * cap, dtype=torch.int32, device=dev),
+                  torch.empty(N * cap, dtype=torch.float32, device=dev))
+        tree_ptr = torch.empty(B + 1, dtype=torch.int32, device=dev)
     a = BiGCNArgs()
-    _fill_args(a, x, batch, rootindex, td, bu, B, training, seed, keep_words, feat_mode, xs, params)
-    tree_ptr = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    _fill_args(a, x, batch, rootindex, (td, bu) if prep is None else prep, B, training, seed, keep_words,
+               feat_mode, xs, params)
     h1 = torch.empty(N, 2 * HID, dtype=torch.float32, device=dev)
     h2 = torch.empty(N, 2 * HID, dtype=torch.float32, device=dev)
     head = torch.empty(B, 4 * HID, dtype=torch.float32, device=dev)
-    a.tree_ptr, a.h1, a.h2, a.head_in = tree_ptr.data_ptr(), h1.data_ptr(), h2.data_ptr(), head.data_ptr()
+    a.tree_ptr, a.h1, a.h2, a.head_in = ptr(tree_ptr), h1.data_ptr(), h2.data_ptr(), head.data_ptr()
     a.save_for_backward = 1 if any(ctx.needs_input_grad) else 0
+    if prep is not None:
+        prep.wait()                                # its preparation ordered before this forward
     ws = workspace(L.bgcn_bigcn_workspace_size(N, B, F, HID), dev)
     check(L.bgcn_bigcn_forward(ctypes.byref(a), ws.data_ptr(), ws.numel(), stream))
     ctx.ws = ws if a.save_for_backward else None   # forward -> backward state (bgcn.h)
     ctx.args = a                                   # the backward reuses the filled struct
-    ctx.graphs = (td, bu)
+    ctx.graphs = (td, bu) if prep is None else (prep,)   # (a prepared buffer lives until the backward)
     ctx.meta = (B, N, params[0].device)
     ctx.has_keep = keep_words is not None
     empty = x.new_empty(0)
-    # saved for autograd's version checks and lifetime (the struct holds their pointers)
-    saved = (x, batch, rootindex, keep_words if keep_words is not None else empty, tree_ptr, h1, h2,
-             *(xs if xs is not None else (empty,) * 4), *params)
-    return head, saved
-
-
-_ENC_SAVED = 11   # tensors of _encoder_forward's `saved` before the parameters
-
-
-def _encoder_forward_prepared(ctx, x, batch, rootindex, B, training, seed, keep_words, feat_mode, params,
-                              stream, prep):
-    N, F = x.shape
-    dev = x.device
-    prep.check_matches(x, batch, rootindex, B, feat_mode)
-    L = _lib.lib()
-    a = BiGCNArgs()
-    a.x, a.ldx, a.num_nodes, a.num_graphs, a.in_feats, a.hid = x.data_ptr(), x.stride(0), N, B, F, HID
-    a.x_dtype = x_dtype_code(x)
-    a.batch, a.rootindex = batch.data_ptr(), rootindex.data_ptr()
-    a.td_w1, a.td_b1, a.td_w2, a.td_b2, a.bu_w1, a.bu_b1, a.bu_w2, a.bu_b2 = (p.data_ptr() for p in params)
-    a.training, a.seed = int(bool(training)), int(seed) & (2**64 - 1)
-    a.keep_words = ptr(keep_words)
-    a.feat_mode = feat_mode
-    a.prepared, a.prepared_bytes = prep.buf.data_ptr(), prep.buf.numel()
-    a.td_num_edges, a.bu_num_edges = prep.td_num_edges, prep.bu_num_edges
-    h1 = torch.empty(N, 2 * HID, dtype=torch.float32, device=dev)
-    h2 = torch.empty(N, 2 * HID, dtype=torch.float32, device=dev)
-    head = torch.empty(B, 4 * HID, dtype=torch.float32, device=dev)
-    a.h1, a.h2, a.head_in = h1.data_ptr(), h2.data_ptr(), head.data_ptr()
-    a.save_for_backward = 1 if any(ctx.needs_input_grad) else 0
-    prep.wait()                                    # its preparation ordered before this forward
-    ws = workspace(L.bgcn_bigcn_workspace_size(N, B, F, HID), dev)
-    check(L.bgcn_bigcn_forward(ctypes.byref(a), ws.data_ptr(), ws.numel(), stream))
-    ctx.ws = ws if a.save_for_backward else None
-    ctx.args = a
-    ctx.graphs = (prep,)                           # the prepared buffer lives until the backward
-    ctx.meta = (B, N, params[0].device)
-    ctx.has_keep = keep_words is not None
-    empty = x.new_empty(0)
-    saved = (x, batch, rootindex, keep_words if keep_words is not None else empty, empty, h1, h2,
-             empty, empty, empty, empty, *params)
-    return head, saved
+    # saved for autograd's version checks and lifetime (the struct holds their pointers); a
+    # prepared batch has no tree_ptr / ELL tensors of its own: empty placeholders
+    saved = (x, batch, rootindex, keep_words if keep_words is not None else empty,
+             tree_ptr if tree_ptr is not None else empty, h1, h2, *(xs if xs is not None else (empty,) * 4))
+    assert len(saved) == _ENC_SAVED
+    return head, saved + tuple(params)
 
 
 class PreparedBatch:
@@ -821,23 +826,12 @@ def prepare_batch(data, degree_on: str = "col", feat_mode: str = "auto", buf: Op
     reference's DropEdge happened in the dataset) on ``stream`` (default: the current
     one), into ``buf`` when it is large enough.  The returned object's event marks the end
     of the preparation; the batch's tensors must be ready on ``stream`` when it runs."""
-    from ._lib import BatchDesc
-    x = features(data.x)
-    td_ei, bu_ei = _check_ei(data.edge_index), _check_ei(data.BU_edge_index)
-    batch = data.batch if data.batch.dtype == torch.int64 and data.batch.is_contiguous() else \
-        data.batch.to(torch.int64).contiguous()
-    root = data.rootindex if data.rootindex.dtype == torch.int64 and data.rootindex.is_contiguous() else \
-        data.rootindex.to(torch.int64).contiguous()
-    _dev_check(x, td_ei, bu_ei, batch, root)
+    d, keep = dense_batch_desc(data)
+    _dev_check(*keep)
+    x = keep[0]
     N, F = x.shape
-    B = int(root.numel())
+    B = int(d.num_graphs)
     code = _feat_code(feat_path(feat_mode, data) if isinstance(feat_mode, str) else feat_mode)
-    d = BatchDesc()
-    d.x, d.ldx, d.num_nodes, d.num_graphs = ptr(x), x.stride(0), N, B
-    d.x_dtype = x_dtype_code(x)
-    d.batch, d.rootindex = ptr(batch), ptr(root)
-    d.td_edge_index, d.td_num_edges = ptr(td_ei), td_ei.size(1)
-    d.bu_edge_index, d.bu_num_edges = ptr(bu_ei), bu_ei.size(1)
     L = _lib.lib()
     n = L.bgcn_prepare_workspace_size(N, B, F, d.td_num_edges, d.bu_num_edges)
     if buf is None or buf.numel() < n:
@@ -848,7 +842,7 @@ def prepare_batch(data, degree_on: str = "col", feat_mode: str = "auto", buf: Op
     ev = torch.cuda.Event()
     ev.record(s)
     return PreparedBatch(buf, N, B, F, int(d.td_num_edges), int(d.bu_num_edges), degree_on,
-                         code == _lib.BGCN_FEAT_DENSE, _prep_key(data), (x, td_ei, bu_ei, batch, root), ev)
+                         code == _lib.BGCN_FEAT_DENSE, _prep_key(data), keep, ev)
 
 
 def _encoder_backward(ctx, saved, dhead, stream):
@@ -928,11 +922,7 @@ def _encoder_inputs(x, batch, rootindex, params, keep_words):
         if p.dtype != torch.float32 or not p.is_contiguous():
             raise ValueError("parameters must be contiguous fp32")
     check_encoder_shapes(x, batch, rootindex, params)
-    if batch.dtype != torch.int64 or not batch.is_contiguous():
-        batch = batch.to(torch.int64).contiguous()
-    if rootindex.dtype != torch.int64 or not rootindex.is_contiguous():
-        rootindex = rootindex.to(torch.int64).contiguous()
-    return batch, rootindex, (keep_words.contiguous() if keep_words is not None else None)
+    return _i64c(batch), _i64c(rootindex), (keep_words.contiguous() if keep_words is not None else None)
 
 
 def bigcn_encoder(x: torch.Tensor, batch: torch.Tensor, rootindex: torch.Tensor, td: Graph, bu: Graph,

@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -27,7 +27,7 @@ from ._lib import BatchDesc, StepArgs, check, ptr, stream_handle, workspace
 from .bigcn import BiGCN, _draw_seed, _num_graphs
 from .dp import GradBucket
 from .feed import PackedBatch
-from .ops import HID, _FEAT_MODES, check_encoder_shapes, degree_code, feat_path, features, x_dtype_code
+from .ops import _i64c, check_encoder_shapes, check_param_shapes, degree_code, dense_batch_desc, feat_path
 from .optim import IMAGE_BU_W1, IMAGE_BU_W2, IMAGE_TD_W1, IMAGE_TD_W2, FusedAdam, bigcn_adam
 
 
@@ -55,12 +55,14 @@ def _step_feat_mode(feat_mode: str, data) -> int:
     return feat_path(feat_mode, data)
 
 
-def _need(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
-    if t.dtype != dtype:
-        t = t.to(dtype)
-    if not t.is_contiguous():
-        t = t.contiguous()
-    return t
+class _Prefetch(NamedTuple):
+    """The next batch a step call prepared on the side lane (``next_data``), held in
+    ``FusedTrainStep._pending`` until a call on that batch consumes it."""
+    batch: object          # matched by identity
+    buf: torch.Tensor      # the prepared-batch buffer the preparation writes
+    key: tuple             # (dense feature path, training): what the preparation was made for
+    keep: tuple            # the tensors the descriptor points into
+    desc: BatchDesc        # with the preparation's DropEdge draw
 
 
 class FusedTrainStep:
@@ -128,7 +130,7 @@ class FusedTrainStep:
         # skipped (bgcn_adam_args.skip_count); read by run_report()
         self.status_seen = torch.zeros(1, dtype=torch.int32, device=model.fc.weight.device)
         self.skipped = torch.zeros(1, dtype=torch.int32, device=model.fc.weight.device)
-        self._pending = None       # (batch, prepared buffer, feat_mode, tensors) from next_data
+        self._pending = None       # the _Prefetch of the last call's next_data
         self._dw1_pending = None   # buffers of a defer_dw1 step until finish_dw1()
         self._stream = None
         self._next_desc = None
@@ -186,33 +188,17 @@ class FusedTrainStep:
         """bgcn_batch of a collated batch (+ the tensors it points into, kept alive);
         ``drop=False``: no DropEdge whatever the model's mode (evaluation batches)."""
         if _compacted(data):
-            F = _in_feats(data)
-            want = [(HID, F), (HID,), (HID, HID + F), (HID,)] * 2
-            for p, shp in zip(self.step_params[:8], want):
-                if tuple(p.shape) != shp:
-                    raise ValueError(f"parameter of shape {tuple(p.shape)}, expected {shp} for in_feats={F}")
-            d = BatchDesc()
+            check_param_shapes(self.step_params[:8], _in_feats(data))
+            d, keep = BatchDesc(), (data,)
             data.fill_desc(d)
-            if drop:
-                self._drop_fields(d)
-            return d, (data,)
-        x = features(data.x)                         # fp32, or bf16 kept as is
-        check_encoder_shapes(x, data.batch, data.rootindex, self.step_params[:8])
-        if data.rootindex.numel() != _num_graphs(data) or data.y.numel() != _num_graphs(data):
-            raise ValueError("rootindex and y must have one entry per tree")
-        td_ei = _need(data.edge_index, torch.int64, "edge_index")
-        bu_ei = _need(data.BU_edge_index, torch.int64, "BU_edge_index")
-        batch = _need(data.batch, torch.int64, "batch")
-        root = _need(data.rootindex, torch.int64, "rootindex")
-        d = BatchDesc()
-        d.x, d.ldx, d.num_nodes, d.num_graphs = ptr(x), x.stride(0), x.size(0), _num_graphs(data)
-        d.x_dtype = x_dtype_code(x)
-        d.batch, d.rootindex = ptr(batch), ptr(root)
-        d.td_edge_index, d.td_num_edges = ptr(td_ei), td_ei.size(1)
-        d.bu_edge_index, d.bu_num_edges = ptr(bu_ei), bu_ei.size(1)
+        else:
+            check_encoder_shapes(data.x, data.batch, data.rootindex, self.step_params[:8])
+            if data.rootindex.numel() != _num_graphs(data) or data.y.numel() != _num_graphs(data):
+                raise ValueError("rootindex and y must have one entry per tree")
+            d, keep = dense_batch_desc(data)
         if drop:
             self._drop_fields(d)
-        return d, (x, td_ei, bu_ei, batch, root)
+        return d, keep
 
     def _drop_fields(self, d) -> None:
         if self.model.training and (self.tddroprate > 0 or self.budroprate > 0):
@@ -251,6 +237,92 @@ class FusedTrainStep:
         self._loss_at = (k + 1) % 4096
         return self._loss_ring[k]
 
+    # One step call (forward_backward / evaluate) in the order both keep: _no_deferred_dw1,
+    # _current, _bind_batches, the call's own outputs, _bind_outputs, _run.
+
+    def _no_deferred_dw1(self) -> None:
+        if self._dw1_pending is not None:
+            # the previous step's conv1 weight gradients are not written yet: a new step
+            # would reuse its workspace and the bucket would keep stale dW1 values
+            raise RuntimeError("a step run with defer_dw1=True is pending: call finish_dw1() first")
+
+    def _current(self, data, training: bool, drop: bool):
+        """The batch a step call runs on: ``(F, y, feat_mode, descriptor, prepared buffer,
+        keep-alive tensors, prepared_ready)``.  The previous call's prefetch is consumed when
+        it was made for this batch (by identity) and this kind of step (its key: a training
+        step's preparation drew DropEdge, an evaluation's did not); otherwise the batch is
+        described here and prepared inside the call."""
+        F = _in_feats(data)
+        y = _i64c(data.y)
+        mode = _step_feat_mode(self.model.feat_mode, data)
+        pend = self._pending
+        if pend is not None and pend.batch is data and pend.key == (mode == _lib.BGCN_FEAT_DENSE, training):
+            # prepared by the previous call (its descriptor, drop seed and inputs)
+            return F, y, mode, pend.desc, pend.buf, pend.keep, 1
+        if pend is not None:       # a preparation no step consumes: order its end before
+            self._join_side()      # its buffer returns to the allocator
+        d, keep = self._desc(data, drop=drop)
+        return F, y, mode, d, self._prep_buffer(d, F), keep, 0
+
+    def _bind_batches(self, cur, next_data, training: bool, seed: int, drop: bool):
+        """The batch fields of ``self._args``: the current batch (``cur`` of _current) and the
+        next one, whose preparation the call forks onto the side lane.  Returns the next
+        batch's _Prefetch (None without ``next_data``), for _run to hold in ``_pending``."""
+        F, _, mode, d, prep, _, ready = cur
+        a = self._args
+        a.cur = d
+        a.in_feats = F
+        a.training, a.seed = int(training), int(seed) & (2**64 - 1)
+        a.feat_mode = mode
+        a.prepared_ready = ready
+        a.prepared, a.prepared_bytes = ptr(prep), prep.numel()
+        self._pending = None
+        if next_data is None:
+            a.next = None
+            a.next_prepared, a.next_prepared_bytes = 0, 0
+            return None
+        nd, nkeep = self._desc(next_data, drop=drop)
+        nbuf = self._prep_buffer(nd, F, avoid=prep)
+        self._next_desc = nd                     # the struct must outlive the call
+        a.next = ctypes.pointer(self._next_desc)
+        a.next_prepared, a.next_prepared_bytes = ptr(nbuf), nbuf.numel()
+        return _Prefetch(next_data, nbuf, (mode == _lib.BGCN_FEAT_DENSE, training), nkeep, nd)
+
+    def _bind_outputs(self, cur, loss, logp, status_flag, defer_dw1: bool):
+        """The labels, outputs, status words and weight images of ``self._args``, and the
+        call's workspace and stream; returns ``(workspace, image buffer)``."""
+        F, y, _, d = cur[:4]
+        a = self._args
+        a.y = ptr(y)
+        a.defer_dw1 = 1 if defer_dw1 else 0
+        a.loss, a.logp, a.status = ptr(loss), ptr(logp), ptr(self.status)
+        a.status_flag = ptr(status_flag)
+        a.status_seen = ptr(self.status_seen)
+        img = self._image_buffer(F)
+        a.images = ptr(img)
+        a.images_current = int(self._images_key is not None and self._images_key == self._image_key())
+        n = _lib.lib().bgcn_train_step_workspace_size(d.num_nodes, d.num_graphs, F, self.num_classes,
+                                                      d.td_num_edges, d.bu_num_edges)
+        ws = self._buffer("ws", n)
+        # every branch the step forks joins back into the caller's stream inside the call
+        # (the workspace can return to the allocator afterwards), except the next batch's
+        # preparation, which outlives the call: its buffer is held in self._pending until
+        # the next call (or _join_side()) has ordered a stream behind it
+        self._stream = stream_handle()   # the prepared buffers belong to this stream
+        return ws, img
+
+    def _run(self, nxt, entry, *args) -> None:
+        """``entry(&self._args, *args, stream)``, a step entry point of the library."""
+        self._pending = nxt              # held before the call: a failure below may leave
+        try:                             # the preparation queued on the side lane
+            check(entry(ctypes.addressof(self._args), *args, self._stream))
+        except Exception:
+            self._dw1_pending = None     # the failed step wrote no gradients to finish
+            if nxt is not None:
+                self._join_side()        # nothing may still write the buffer once it is freed
+                self._pending = None
+            raise
+
     def forward_backward(self, data, seed: Optional[int] = None, logp: Optional[torch.Tensor] = None,
                          next_data=None, defer_dw1: bool = False, adam=None):
         """bgcn_train_step only (no all-reduce, no optimiser step); returns the loss.
@@ -263,78 +335,20 @@ class FusedTrainStep:
 
         ``defer_dw1``: return before the conv1 weight gradients are written (every other
         gradient and the status slot are final); ``finish_dw1()`` writes them."""
-        if self._dw1_pending is not None:
-            # the previous step's conv1 weight gradients are not written yet: a new step
-            # would reuse its workspace and the bucket would keep stale dW1 values
-            raise RuntimeError("a step run with defer_dw1=True is pending: call finish_dw1() first")
+        self._no_deferred_dw1()
         m = self.model
-        F = _in_feats(data)
-        dev = _device(data)
-        y = _need(data.y, torch.int64, "y")
         if seed is None:
             seed = _draw_seed() if m.training else 0
-        mode = _step_feat_mode(m.feat_mode, data)
-        pend = self._pending
-        if pend is not None and pend[0] is data and pend[2] == (mode == _lib.BGCN_FEAT_DENSE, m.training):
-            # prepared by the previous call (its descriptor, drop seed and inputs)
-            prep, keep, d = pend[1], pend[3], pend[4]
-            ready = 1
-        else:
-            if pend is not None:   # a preparation no step consumes: order its end before
-                self._join_side()   # its buffer returns to the allocator
-            d, keep = self._desc(data)
-            prep = self._prep_buffer(d, F)
-            ready = 0
-        a = self._args
-        a.cur = d
-        a.in_feats = F
-        a.y = ptr(y)
-        a.training, a.seed = int(m.training), int(seed) & (2**64 - 1)
-        a.feat_mode = mode
-        a.prepared_ready = ready
-        a.prepared, a.prepared_bytes = ptr(prep), prep.numel()
-        a.defer_dw1 = 1 if defer_dw1 else 0
-        a.adam = ctypes.addressof(adam) if adam is not None else None   # (the optimiser's own struct)
-        self._pending = None
-        nxt = None
-        if next_data is not None:
-            nd, nkeep = self._desc(next_data)
-            nbuf = self._prep_buffer(nd, F, avoid=prep)
-            self._next_desc = nd                     # the struct must outlive the call
-            a.next = ctypes.pointer(self._next_desc)
-            a.next_prepared, a.next_prepared_bytes = ptr(nbuf), nbuf.numel()
-            nxt = (next_data, nbuf, (mode == _lib.BGCN_FEAT_DENSE, m.training), nkeep, nd)
-        else:
-            a.next = None
-            a.next_prepared, a.next_prepared_bytes = 0, 0
-        self.last_drop_seed = int(a.cur.drop_seed) if a.cur.td_droprate > 0 or a.cur.bu_droprate > 0 else None
-        loss = self._loss_slot(dev)
-        a.loss, a.logp, a.status = ptr(loss), ptr(logp), ptr(self.status)
-        a.status_flag = ptr(self.bucket.flag)
-        a.status_seen = ptr(self.status_seen)
-        img = self._image_buffer(F)
-        a.images = ptr(img)
-        a.images_current = int(self._images_key is not None and self._images_key == self._image_key())
-        L = _lib.lib()
-        N, B = d.num_nodes, d.num_graphs
-        ws = self._buffer("ws", L.bgcn_train_step_workspace_size(N, B, F, self.num_classes, d.td_num_edges,
-                                                                 d.bu_num_edges))
-        # every branch the step forks joins back into the caller's stream inside the call
-        # (the workspace can return to the allocator afterwards), except the next batch's
-        # preparation, which outlives the call: its buffer is held in self._pending until
-        # the next call (or _join_side()) has ordered a stream behind it
-        self._stream = stream_handle()   # the prepared buffers belong to this stream
-        self._last = (ws, N, B, F)       # the saved activations of this step (saved_activations)
+        cur = self._current(data, m.training, drop=True)
+        nxt = self._bind_batches(cur, next_data, m.training, seed, drop=True)
+        F, y, _, d, prep, keep, _ = cur
+        self.last_drop_seed = int(d.drop_seed) if d.td_droprate > 0 or d.bu_droprate > 0 else None
+        loss = self._loss_slot(_device(data))
+        ws, img = self._bind_outputs(cur, loss, logp, self.bucket.flag, defer_dw1)
+        self._args.adam = ctypes.addressof(adam) if adam is not None else None   # (the optimiser's own struct)
+        self._last = (ws, d.num_nodes, d.num_graphs, F)   # the saved activations of this step (saved_activations)
         self._dw1_pending = (ws, prep, keep, y, img) if defer_dw1 else None
-        self._pending = nxt              # held before the call: a failure below may leave
-        try:                             # the preparation queued on the side lane
-            check(L.bgcn_train_step(ctypes.addressof(a), ptr(ws), ws.numel(), self._stream))
-        except Exception:
-            self._dw1_pending = None     # the failed step wrote no gradients to finish
-            if nxt is not None:
-                self._join_side()        # nothing may still write the buffer once it is freed
-                self._pending = None
-            raise
+        self._run(nxt, _lib.lib().bgcn_train_step, ptr(ws), ws.numel())
         return loss
 
     def evaluate(self, data, next_data=None, logp: Optional[torch.Tensor] = None, pred: bool = False):
@@ -349,71 +363,19 @@ class FusedTrainStep:
         int64 device tensor) when ``pred=True``.  ``logp``: an optional [B, C] fp32 output
         for the log-probabilities.  ``next_data``: the next evaluation batch, prepared on the
         side lane during this call.  Validity: ``check_status()`` / ``run_report()``."""
-        if self._dw1_pending is not None:
-            raise RuntimeError("a step run with defer_dw1=True is pending: call finish_dw1() first")
-        m = self.model
-        F = _in_feats(data)
-        dev = _device(data)
-        y = _need(data.y, torch.int64, "y")
-        mode = _step_feat_mode(m.feat_mode, data)
-        key = (mode == _lib.BGCN_FEAT_DENSE, False)
-        pend = self._pending
-        if pend is not None and pend[0] is data and pend[2] == key:
-            prep, keep, d = pend[1], pend[3], pend[4]
-            ready = 1
-        else:
-            if pend is not None:
-                self._join_side()
-            d, keep = self._desc(data, drop=False)
-            prep = self._prep_buffer(d, F)
-            ready = 0
+        self._no_deferred_dw1()
+        cur = self._current(data, False, drop=False)
+        B = cur[3].num_graphs
         if logp is not None and (logp.dtype != torch.float32 or not logp.is_contiguous()
-                                 or logp.numel() != d.num_graphs * self.num_classes):
+                                 or logp.numel() != B * self.num_classes):
             raise ValueError("logp must be a contiguous fp32 [B, C] tensor")
-        a = self._args
-        a.cur = d
-        a.in_feats = F
-        a.y = ptr(y)
-        a.training, a.seed = 0, 0
-        a.feat_mode = mode
-        a.prepared_ready = ready
-        a.prepared, a.prepared_bytes = ptr(prep), prep.numel()
-        a.defer_dw1 = 0
-        self._pending = None
-        nxt = None
-        if next_data is not None:
-            nd, nkeep = self._desc(next_data, drop=False)
-            nbuf = self._prep_buffer(nd, F, avoid=prep)
-            self._next_desc = nd
-            a.next = ctypes.pointer(self._next_desc)
-            a.next_prepared, a.next_prepared_bytes = ptr(nbuf), nbuf.numel()
-            nxt = (next_data, nbuf, key, nkeep, nd)
-        else:
-            a.next = None
-            a.next_prepared, a.next_prepared_bytes = 0, 0
+        nxt = self._bind_batches(cur, next_data, False, 0, drop=False)
+        dev = _device(data)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         correct = torch.empty(1, dtype=torch.int32, device=dev)
-        pr = torch.empty(d.num_graphs, dtype=torch.int64, device=dev) if pred else None
-        a.loss, a.logp, a.status = ptr(loss), ptr(logp), ptr(self.status)
-        a.status_flag = None
-        a.status_seen = ptr(self.status_seen)
-        img = self._image_buffer(F)
-        a.images = ptr(img)
-        current = self._images_key is not None and self._images_key == self._image_key()
-        a.images_current = int(current)
-        L = _lib.lib()
-        N, B = d.num_nodes, d.num_graphs
-        ws = self._buffer("ws", L.bgcn_train_step_workspace_size(N, B, F, self.num_classes, d.td_num_edges,
-                                                                 d.bu_num_edges))
-        self._stream = stream_handle()
-        self._pending = nxt
-        try:
-            check(L.bgcn_eval_step(ctypes.addressof(a), ptr(correct), ptr(pr), ptr(ws), ws.numel(), self._stream))
-        except Exception:
-            if nxt is not None:
-                self._join_side()
-                self._pending = None
-            raise
+        pr = torch.empty(B, dtype=torch.int64, device=dev) if pred else None
+        ws, _ = self._bind_outputs(cur, loss, logp, None, False)
+        self._run(nxt, _lib.lib().bgcn_eval_step, ptr(correct), ptr(pr), ptr(ws), ws.numel())
         # (stale images were re-derived into the buffer on the sparse path only, so the key
         # is left as it was: after a training step's Adam they are current anyway)
         out = (loss.view(()), correct.view(()))

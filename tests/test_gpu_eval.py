@@ -109,6 +109,17 @@ def test_eval_step_full_size_vs_oracle(workload):
     assert torch.equal(loss, loss0) and torch.equal(correct, correct0)
 
 
+def _small(seed):
+    """Trees of 1, 2 and 40 nodes, F = 64, 4 classes, one row of 33 non-zeros (one entry in
+    the spill pool)."""
+    from bigcn_amd.data import synth_batch
+    b = synth_batch(np.random.default_rng(seed), [1, 2, 40], 64, 4, 0.0, 0.0, device=DEV)
+    b.x[17].zero_()
+    b.x[17, 5:38] = 1.0
+    assert int((b.x[17] != 0).sum()) == 33
+    return b
+
+
 def test_eval_step_preparing_its_own_batch_matches_a_batch_prepared_ahead():
     """An evaluation step that prepares its batch inside the call (prepared_ready = 0, no next
     batch: K1 on the side lane beside the pass over X and the CSC of X as separate launches)
@@ -117,13 +128,9 @@ def test_eval_step_preparing_its_own_batch_matches_a_batch_prepared_ahead():
     entry in the spill pool).  Both preparations build the same lists in the same order, so
     loss, log-probabilities and predictions are compared bit for bit."""
     from bigcn_amd import FusedTrainStep
-    from bigcn_amd.data import synth_batch
     from bigcn_amd.ops import prepare_batch
-    rng = np.random.default_rng(7)
-    b = synth_batch(rng, [1, 2, 40], 64, 4, 0.0, 0.0, device=DEV)
-    b.x[17].zero_()
-    b.x[17, 5:38] = 1.0
-    assert int((b.x[17] != 0).sum()) == 33
+    from bigcn_amd.train import _Prefetch
+    b = _small(7)
     m = _model(O.make_params(64, 64, 64, 4, seed=33), 64)
     m.eval()
     st = FusedTrainStep(m)
@@ -132,7 +139,8 @@ def test_eval_step_preparing_its_own_batch_matches_a_batch_prepared_ahead():
     assert st._args.prepared_ready == 0 and not st._args.next
     ahead = prepare_batch(b, m.degree_on, "auto")
     d, keep = st._desc(b, drop=False)
-    st._pending = (b, ahead.buf, (False, False), keep, d)     # as a previous call's prefetch leaves it
+    # as a previous call's prefetch leaves it
+    st._pending = _Prefetch(batch=b, buf=ahead.buf, key=(False, False), keep=keep, desc=d)
     logp1 = torch.empty(3, 4, device=DEV)
     loss1, correct1, pred1 = st.evaluate(b, logp=logp1, pred=True)
     assert st._args.prepared_ready == 1 and st._args.prepared == ahead.buf.data_ptr()
@@ -143,6 +151,69 @@ def test_eval_step_preparing_its_own_batch_matches_a_batch_prepared_ahead():
     rloss, rlogp = _oracle_eval(b, O.make_params(64, 64, 64, 4, seed=33))
     close(logp, rlogp, what="logp")
     close(loss, rloss, what="loss")
+
+
+def test_prefetch_made_for_a_training_step_is_not_consumed_by_an_evaluation():
+    """forward_backward(b0, next_data=b1) in training mode prepares b1 with its DropEdge draw;
+    evaluate(b1) must not take that preparation (the record's key differs in `training`): it
+    prepares b1 itself, undropped, and gives the bits of a fresh object's evaluate(b1).  The
+    discarded preparation still consumed one drop seed: batch k prepared by the object uses
+    drop_seed + k, whether a step consumes the preparation or not."""
+    from bigcn_amd import FusedTrainStep
+    b0, b1 = _small(7), _small(8)
+    p = O.make_params(64, 64, 64, 4, seed=33)
+    out = []
+    for prefetch in (True, False):
+        m = _model(p, 64)
+        m.train()
+        st = FusedTrainStep(m, tddroprate=0.2, budroprate=0.2, drop_seed=100)
+        if prefetch:
+            st.forward_backward(b0, seed=1, next_data=b1)
+            assert st.last_drop_seed == 100 and st._pending is not None
+        logp = torch.empty(3, 4, device=DEV)
+        loss, correct, pred = st.evaluate(b1, logp=logp, pred=True)
+        assert st._args.prepared_ready == 0 and st._pending is None
+        torch.cuda.synchronize()
+        st.check_status()
+        out.append((loss.clone(), logp, pred, correct.clone()))
+        if prefetch:
+            st.forward_backward(b1, seed=2)
+            assert st.last_drop_seed == 102      # b0: 100, the discarded preparation of b1: 101
+            torch.cuda.synchronize()
+            st.check_status()
+    for got, want in zip(*out):
+        assert torch.equal(got, want)
+
+
+def test_rejected_step_call_leaves_no_state_behind():
+    """A step call the library rejects at its argument checks (the current batch's x is not
+    16-byte aligned: check_batch, before any launch) raises BGCNError and leaves neither the
+    next batch's prefetch record nor the deferred-dW1 buffers behind; the next step on the
+    object gives the bits of that step on a fresh object."""
+    from bigcn_amd import FusedTrainStep
+    from bigcn_amd._lib import BGCNError
+    from bigcn_amd.data import Batch
+    b0, b1 = _small(7), _small(8)
+    bad = Batch(**b0.__dict__)
+    bad.x = torch.empty(b0.x.numel() + 1, device=DEV)[1:].view_as(b0.x).copy_(b0.x)
+    assert bad.x.is_contiguous() and bad.x.data_ptr() % 16 == 4
+    p = O.make_params(64, 64, 64, 4, seed=33)
+    out = []
+    for reject in (True, False):
+        m = _model(p, 64)
+        m.train()
+        st = FusedTrainStep(m)
+        if reject:
+            with pytest.raises(BGCNError, match="16-byte aligned"):
+                st.forward_backward(bad, seed=3, next_data=b1, defer_dw1=True)
+            assert st._pending is None and st._dw1_pending is None
+        loss = st.forward_backward(b0, seed=5)
+        torch.cuda.synchronize()
+        st.check_status()
+        out.append([loss.clone()] + [g.clone() for g in st.grads().values()])
+    assert len(out[0]) == 11
+    for got, want in zip(*out):
+        assert torch.equal(got, want)
 
 
 def test_eval_step_matches_per_op_model_and_training_loss():

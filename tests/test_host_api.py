@@ -41,6 +41,79 @@ def test_fused_step_takes_the_models_degree_convention():
         FusedTrainStep(m, degree_on="col")
 
 
+def _cpu_batch(dtype=torch.float32, awkward=False):
+    """Trees of 1, 2 and 40 nodes, F = 16; awkward: the index tensors arrive as int32
+    (batch, edge_index) or non-contiguous (rootindex, BU_edge_index) and must be converted."""
+    import numpy as np
+    from bigcn_amd.data import synth_batch
+    b = synth_batch(np.random.default_rng(3), [1, 2, 40], 16, 4, 0.0, 0.0, dtype=dtype)
+    if awkward:
+        b.batch, b.edge_index = b.batch.to(torch.int32), b.edge_index.to(torch.int32)
+        b.rootindex = torch.stack([b.rootindex, b.rootindex], 1)[:, 0]
+        b.BU_edge_index = b.BU_edge_index.t().contiguous().t()
+        assert not b.rootindex.is_contiguous() and not b.BU_edge_index.is_contiguous()
+    return b
+
+
+def _dense_fields(d):
+    return {k: getattr(d, k) for k in ("x", "ldx", "num_nodes", "num_graphs", "x_dtype", "batch", "rootindex",
+                                       "td_edge_index", "td_num_edges", "bu_edge_index", "bu_num_edges")}
+
+
+@pytest.mark.parametrize("case", ["fp32", "bf16", "converted"])
+def test_dense_batch_descriptor(case):
+    """ops.dense_batch_desc (the one place a dense batch's bgcn_batch is filled, for the fused
+    step and prepare_batch alike): every field, and the keep-alive tuple owns every pointer."""
+    from bigcn_amd import _lib
+    from bigcn_amd.ops import dense_batch_desc
+    b = _cpu_batch(torch.bfloat16 if case == "bf16" else torch.float32, awkward=case == "converted")
+    d, keep = dense_batch_desc(b)
+    x, td, bu, batch, root = keep
+    assert _dense_fields(d) == {
+        "x": x.data_ptr(), "ldx": 16, "num_nodes": 43, "num_graphs": 3,
+        "x_dtype": _lib.BGCN_DTYPE_BF16 if case == "bf16" else _lib.BGCN_DTYPE_F32,
+        "batch": batch.data_ptr(), "rootindex": root.data_ptr(),
+        "td_edge_index": td.data_ptr(), "td_num_edges": 40, "bu_edge_index": bu.data_ptr(), "bu_num_edges": 40}
+    assert (d.td_droprate, d.bu_droprate, d.drop_seed) == (0.0, 0.0, 0)
+    assert not d.x_row_ptr and not d.x_col and not d.x_val
+    assert x.dtype == b.x.dtype and x.is_contiguous() and x.shape == (43, 16)
+    for t, src in ((td, b.edge_index), (bu, b.BU_edge_index), (batch, b.batch), (root, b.rootindex)):
+        assert t.dtype == torch.int64 and t.is_contiguous() and torch.equal(t, src.to(torch.int64))
+        assert (t is src) == (case != "converted")     # converted only when it has to be
+    assert x.data_ptr() == b.x.data_ptr()
+
+
+def test_fused_step_desc_is_the_dense_descriptor_plus_dropedge():
+    """FusedTrainStep._desc = dense_batch_desc + the DropEdge fields: batch k described with
+    drop=True under model.training and a non-zero rate uses drop seed drop_seed + k; no draw
+    (and no increment) with drop=False, in eval mode, or with both rates 0."""
+    from bigcn_amd import FusedTrainStep
+    from bigcn_amd.ops import dense_batch_desc
+    b = _cpu_batch()
+    want = _dense_fields(dense_batch_desc(b)[0])
+    m = BiGCN(16, 64, 64)
+    st = FusedTrainStep(m, tddroprate=0.25, budroprate=0.5, drop_seed=2**64 - 2)
+    m.train()
+    seeds = []
+    for drop, training in ((True, True), (False, True), (True, False), (True, True), (True, True)):
+        m.train(training)
+        d, keep = st._desc(b) if drop else st._desc(b, drop=False)
+        assert _dense_fields(d) == want and len(keep) == 5 and keep[0].data_ptr() == b.x.data_ptr()
+        if drop and training:
+            assert (d.td_droprate, d.bu_droprate) == (0.25, 0.5)
+            seeds.append(int(d.drop_seed))
+        else:
+            assert (d.td_droprate, d.bu_droprate, d.drop_seed) == (0.0, 0.0, 0)
+    assert seeds == [2**64 - 2, 2**64 - 1, 0] and st._drop_count == 3      # (the seed wraps at 2^64)
+    m.train()
+    plain = FusedTrainStep(m)
+    d, _ = plain._desc(b)
+    assert (d.td_droprate, d.bu_droprate, d.drop_seed) == (0.0, 0.0, 0) and plain._drop_count == 0
+    b.rootindex = b.rootindex[:2]
+    with pytest.raises(ValueError, match="one entry per tree"):
+        st._desc(b)
+
+
 def test_fused_step_bucket_carries_the_status_slot():
     """Layout [early gradients | status slot | conv1 weight gradients]: part a (flat_a)
     holds every gradient the deferred-dW1 step finishes first and the status slot, part b
