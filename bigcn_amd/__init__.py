@@ -9,6 +9,9 @@ Drop-in symbols for the reference's hot path (cwkd/BiGCN):
   the edge-inference kernel (``edge_infer``), reference checkpoints load strictly
 * ``explain`` / ``segment_rank`` - the reference's analysis (explain_PHEME.py): per-stage node sums and
   per-tree rankings of a whole batch, for ``BiGCN`` / ``Net`` / ``EBGCN`` in eval mode
+* ``compare`` / ``tree_centrality`` / ``rank_similarity`` - the reference's comparison
+  (compare_similarity.py): the trees' graph centralities and, per tree, five similarity statistics of
+  every pair of rankings
 * ``FusedTrainStep`` - the training-loop body (BiGCN_Twitter.py:183-189) as one native call
   + the data-parallel all-reduce + fused Adam
 
@@ -16,6 +19,7 @@ all backed by hand-written HIP kernels in ``libbgcn.so`` (C ABI: ``include/bgcn.
 """
 from .bigcn import BiGCN, BUrumorGCN, Net, TDrumorGCN, make_optimizer
 from .conv import GCNConv
+from .compare import compare, rank_similarity, tree_centrality
 from .ebgcn import EBGCN
 from .explain import explain, segment_rank
 from .ops import Graph, bigcn_encoder, build_graph, edge_infer, gcn_conv, scatter_mean, spmm
@@ -24,5 +28,6 @@ from .train import FusedTrainStep
 
 __all__ = ["GCNConv", "scatter_mean", "TDrumorGCN", "BUrumorGCN", "BiGCN", "Net", "make_optimizer",
            "Graph", "build_graph", "gcn_conv", "spmm", "bigcn_encoder", "FusedAdam", "bigcn_adam",
-           "FusedTrainStep", "EBGCN", "edge_infer", "explain", "segment_rank"]
+           "FusedTrainStep", "EBGCN", "edge_infer", "explain", "segment_rank",
+           "compare", "tree_centrality", "rank_similarity"]
 __version__ = "0.1.0"

@@ -36,6 +36,10 @@ ABI_VERSION = 12   # BGCN_ABI_VERSION of include/bgcn.h
 BGCN_STATUS_CROSS_TREE = 16
 BGCN_EDGE_INFER_TILE = 32   # edges per workgroup of bgcn_edge_infer
 BGCN_SEGMENT_RANK_LDS = 4096   # longest segment bgcn_segment_rank sorts in LDS
+BGCN_TREE_CENTRALITY_LDS = 2048   # longest tree bgcn_tree_centrality keeps in LDS
+BGCN_RANK_SIMILARITY_MAX = 32   # most rankings, and the largest k, of bgcn_rank_similarity
+BGCN_STATUS_TWO_PARENTS = 32
+BGCN_STATUS_CYCLE = 64
 
 # every symbol include/bgcn.h declares (checked by tests/test_capi.py)
 EXPORTED_SYMBOLS = (
@@ -58,6 +62,8 @@ EXPORTED_SYMBOLS = (
     "bgcn_loader_wait", "bgcn_loader_get_stats",
     "bgcn_bn_fold", "bgcn_edge_infer", "bgcn_ebgcn_conv2_lin_workspace_size", "bgcn_ebgcn_conv2_lin",
     "bgcn_explain_sums_workspace_size", "bgcn_explain_sums", "bgcn_segment_rank_workspace_size", "bgcn_segment_rank",
+    "bgcn_tree_centrality_workspace_size", "bgcn_tree_centrality", "bgcn_rank_similarity_workspace_size",
+    "bgcn_rank_similarity",
 )
 
 
@@ -219,6 +225,12 @@ _SIGS = {
     "bgcn_segment_rank_workspace_size": (c_size_t, [c_int64]),
     "bgcn_segment_rank": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_size_t, c_void_p]),
+    "bgcn_tree_centrality_workspace_size": (c_size_t, [c_int64, c_int64]),
+    "bgcn_tree_centrality": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
+    "bgcn_rank_similarity_workspace_size": (c_size_t, [c_int64]),
+    "bgcn_rank_similarity": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

@@ -313,6 +313,13 @@ int explain_sums_impl(const float* h1, int64_t ldh1, const float* h2, int64_t ld
   return BGCN_OK;
 }
 
+int seg_bounds_impl(const int64_t* batch, int64_t N, int64_t B, int32_t* seg, int32_t* status, hipStream_t s) {
+  BGCN_CHECK_HIP(hipMemsetAsync(seg, 0, (size_t(B) + 2) * sizeof(int32_t), s));
+  hipLaunchKernelGGL(k_seg_bounds, dim3(grid_for(N + 1, 256)), dim3(256), 0, s, batch, N, B, seg, seg + B + 1, status);
+  BGCN_CHECK_LAUNCH();
+  return BGCN_OK;
+}
+
 int segment_rank_impl(const float* values, int64_t ld, int64_t S, const int64_t* batch, int64_t N, int64_t B,
                       int32_t* order, float* sorted, int32_t* status, void* ws, size_t ws_bytes, hipStream_t s) {
   BGCN_CHECK_ARG(N >= 0 && B >= 0 && S >= 0, "segment_rank: negative size");
@@ -326,9 +333,7 @@ int segment_rank_impl(const float* values, int64_t ld, int64_t S, const int64_t*
   Carve c(ws, ws_bytes);
   carve_rank(c, B, &w);
   BGCN_CHECK_ARG(ws && c.ok(), "segment_rank: workspace too small");
-  BGCN_CHECK_HIP(hipMemsetAsync(w.seg, 0, (size_t(B) + 2) * sizeof(int32_t), s));
-  hipLaunchKernelGGL(k_seg_bounds, dim3(grid_for(N + 1, 256)), dim3(256), 0, s, batch, N, B, w.seg, w.bad, status);
-  BGCN_CHECK_LAUNCH();
+  BGCN_TRY(seg_bounds_impl(batch, N, B, w.seg, status, s));
   hipLaunchKernelGGL(k_segment_rank, dim3(unsigned(B), unsigned(S), kRankSplit), dim3(256), 0, s, values, ld, N,
                      w.seg, w.bad, order, sorted);
   BGCN_CHECK_LAUNCH();

@@ -438,6 +438,11 @@ size_t carve_prepared(Carve& c, int64_t N, int64_t B, int64_t F, int64_t Etd, in
 // bgcn_bigcn_forward / _backward on a caller's prepared batch (bgcn_bigcn_args.prepared)
 int bigcn_prepared_call(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, hipStream_t s, bool backward);
 
+// ---- segment bounds of a PyG batch vector (bgcn_explain.hip, k_seg_bounds): seg [B + 2] int32,
+// seg[t] = first node of tree t, seg[B] = N, seg[B + 1] = `bad` (nonzero, with status bit 0: the
+// vector decreases or holds an id outside [0, B); the bounds are then not to be used)
+int seg_bounds_impl(const int64_t* batch, int64_t N, int64_t B, int32_t* seg, int32_t* status, hipStream_t s);
+
 // ---- DropEdge (bgcn_drop.hip)
 size_t drop_ws_size(int64_t B);
 int drop_edges_impl(const int64_t* td, int64_t Etd, int64_t* td_out, int64_t ld_td, double td_rate,

@@ -11,6 +11,9 @@
   BatchNorm'd concat.
 * :func:`explain_sums` / :func:`segment_rank` - the reference's analysis (``explain_PHEME.py``):
   per-node stage sums without the concat, and a batched per-tree ``topk(k = n)``.
+* :func:`tree_centrality` / :func:`rank_similarity` - the reference's comparison
+  (``compare_similarity.py``): the trees' graph centralities and the per-tree similarity
+  statistics of every pair of rankings.
 * :func:`bigcn_encoder` - the fused TD+BU encoder of ``BiGCN.forward``
   (``model/Twitter/BiGCN_Twitter.py:125-128``), all of K1-K10 on the GPU.
 
@@ -612,6 +615,99 @@ def segment_rank(values: torch.Tensor, batch: torch.Tensor, num_graphs: int):
     if int(status.item()) & 1:
         raise IndexError("segment_rank: batch must be non-decreasing with ids in [0, num_graphs)")
     return order, srt
+
+
+# ----------------------------------------------------------------------------- compare
+TREE_CENTRALITY_LDS = _lib.BGCN_TREE_CENTRALITY_LDS   # longest tree the centrality kernel keeps in LDS
+RANK_SIMILARITY_MAX = _lib.BGCN_RANK_SIMILARITY_MAX   # most rankings, and the largest k, of rank_similarity
+# the reference's names (compare_similarity.py:41-43), in its order
+CENTRALITY_NAMES = ("out_degree", "betweenness", "closeness")
+METRIC_NAMES = ("pearsonr", "spearmanr", "kendalltau", "somersd", "jaccard")
+
+
+def _raise_on_compare_status(s: int) -> None:
+    """The Python errors of the status word bgcn_tree_centrality / bgcn_rank_similarity leave."""
+    if s & _lib.BGCN_STATUS_TWO_PARENTS:
+        raise ValueError("tree_centrality: a node has more than one incoming edge (not a tree)")
+    if s & _lib.BGCN_STATUS_CROSS_TREE:
+        raise ValueError("tree_centrality: an edge joins two trees of the batch")
+    if s & _lib.BGCN_STATUS_CYCLE:
+        raise ValueError("tree_centrality: the edges of a tree hold a cycle")
+    if s & 1:
+        raise IndexError("an edge endpoint is out of range, or batch is not non-decreasing with ids in "
+                         "[0, num_graphs)")
+    if s & 2:
+        raise ValueError("rank_similarity: a list repeats a node index (or holds one outside its tree) inside its "
+                         "first k entries: not a ranking")
+
+
+def _num_graphs_of(batch: torch.Tensor, num_graphs: Optional[int]) -> int:
+    if num_graphs is not None:
+        return int(num_graphs)
+    return int(batch[-1].item()) + 1 if batch.numel() else 0   # (a host sync: pass num_graphs to avoid it)
+
+
+def _tree_centrality(edge_index: torch.Tensor, batch: torch.Tensor, num_graphs: int, status: torch.Tensor):
+    _dev_check(edge_index, batch)
+    if edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise ValueError("tree_centrality: edge_index must be [2, E]")
+    edge_index, batch = edge_index.to(torch.int64).contiguous(), batch.to(torch.int64).contiguous()
+    N, E = batch.numel(), edge_index.size(1)
+    cent = torch.zeros(3, N, dtype=torch.float32, device=batch.device)
+    L = _lib.lib()
+    ws = workspace(L.bgcn_tree_centrality_workspace_size(N, num_graphs), batch.device)
+    check(L.bgcn_tree_centrality(ptr(edge_index), E, ptr(batch), N, num_graphs, ptr(cent), max(N, 1), ptr(status),
+                                 ptr(ws), ws.numel(), stream_handle()))
+    return cent
+
+
+def tree_centrality(edge_index: torch.Tensor, batch: torch.Tensor, num_graphs: Optional[int] = None,
+                    validate: bool = False, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``[3, N]`` fp32, rows :data:`CENTRALITY_NAMES`: networkx's ``out_degree_centrality``,
+    ``betweenness_centrality`` and ``closeness_centrality`` (default arguments) of every tree of the
+    batch, from the top-down ``edge_index`` [2, E] (parent -> child, any edge order) and the PyG
+    ``batch`` vector (``bgcn_tree_centrality``).  Nodes of a tree with equal child count, depth and
+    subtree size get bit-equal values.  A DropEdge'd forest is accepted.  A node with two parents, an
+    edge across trees, a cycle, an endpoint out of range or a bad ``batch`` sets ``status`` (int32
+    [1], optional) and leaves the tree's values zero; ``validate=True`` syncs and raises ValueError /
+    IndexError.  ``num_graphs=None`` reads it from ``batch`` (a host sync)."""
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=batch.device)
+    cent = _tree_centrality(edge_index, batch, _num_graphs_of(batch, num_graphs), status)
+    if validate:
+        _raise_on_compare_status(int(status.item()))
+    return cent
+
+
+def _rank_similarity(orders: torch.Tensor, batch: torch.Tensor, k: int, num_graphs: int, status: torch.Tensor):
+    _dev_check(orders, batch)
+    if orders.dim() == 1:
+        orders = orders.unsqueeze(0)
+    if orders.dim() != 2 or orders.size(1) != batch.numel():
+        raise ValueError("rank_similarity: orders must be [V, N] (or [N]) with batch [N]")
+    orders, batch = orders.to(torch.int32).contiguous(), batch.to(torch.int64).contiguous()
+    V, N = orders.shape
+    sim = torch.zeros(num_graphs, len(METRIC_NAMES), V, V, dtype=torch.float64, device=orders.device)
+    valid = torch.zeros(num_graphs, dtype=torch.int32, device=orders.device)
+    L = _lib.lib()
+    ws = workspace(L.bgcn_rank_similarity_workspace_size(num_graphs), orders.device)
+    check(L.bgcn_rank_similarity(ptr(orders), max(N, 1), V, ptr(batch), N, num_graphs, int(k), ptr(sim), ptr(valid),
+                                 ptr(status), ptr(ws), ws.numel(), stream_handle()))
+    return sim, valid
+
+
+def rank_similarity(orders: torch.Tensor, batch: torch.Tensor, k: int = 10, num_graphs: Optional[int] = None):
+    """``(sim [B, 5, V, V] float64, valid [B] bool)``: the body of ``compute_metrics``
+    (``compare_similarity.py:88-171``) for every tree of a batch (``bgcn_rank_similarity``).
+    ``orders`` [V, N] int32 are V rankings as :func:`segment_rank` gives them; for every tree of more
+    than ``k`` nodes and every pair of rankings the five statistics :data:`METRIC_NAMES` over their
+    first ``k`` entries.  A tree of at most ``k`` nodes gets zeros and ``valid`` False (the
+    reference skips it).  ``k`` in [2, 32], V in [1, 32].  One host sync at the end: a list that
+    repeats an index inside its first ``k`` raises ValueError, a bad ``batch`` IndexError."""
+    status = torch.zeros(1, dtype=torch.int32, device=orders.device)
+    sim, valid = _rank_similarity(orders, batch, k, _num_graphs_of(batch, num_graphs), status)
+    _raise_on_compare_status(int(status.item()))
+    return sim, valid.bool()
 
 
 # ----------------------------------------------------------------------------- fused encoder

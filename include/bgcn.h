@@ -308,6 +308,60 @@ int bgcn_segment_rank(const float* values, int64_t ld, int64_t num_stages, const
                       int32_t* status, void* workspace, size_t workspace_bytes, bgcn_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * Compare (compare_similarity.py:38-183): the reference scores, per tree, every pair of node
+ * rankings - by three graph centralities and by the models' stage sums - with five statistics
+ * over the rankings' first k entries.  Additive entry points: BGCN_ABI_VERSION is unchanged.
+ *
+ * bgcn_tree_centrality: cent [3, num_nodes] fp32 (row stride ld), rows out_degree, betweenness,
+ * closeness (the reference's order), of the top-down edge list edge_index int64 [2, num_edges]
+ * (parent -> child, global node ids, any edge order) and the PyG batch vector.  The script that
+ * wrote the reference's centrality files is not part of it; the definition taken here is
+ * networkx's out_degree_centrality, betweenness_centrality and closeness_centrality on the
+ * DiGraph of a tree's edges with default arguments, which for a tree of n nodes and a node of c
+ * children, depth d and subtree size s (itself included) are
+ *   out_degree = c / (n - 1) (1 when n = 1)     betweenness = d (s - 1) / ((n - 1)(n - 2)) (0 when
+ *   n <= 2)     closeness = 2 d / ((d + 1)(n - 1)) (0 when d = 0).
+ * c, d, s, n are computed exactly in integers; each value is one fp64 division rounded once to
+ * fp32, so nodes with equal (c, d, s) get bit-equal values and bgcn_segment_rank's tie rule
+ * (ascending node index) decides between them.  One workgroup per tree: depths and subtree sizes
+ * by pointer jumping (ceil(log2 n) rounds, integer atomics only), in LDS for a tree of at most
+ * BGCN_TREE_CENTRALITY_LDS nodes, on a workspace slice for a longer one.  Deterministic.
+ * A forest is accepted (a DropEdge'd list: several parentless nodes per tree; depth and subtree
+ * size are then per component, n stays the tree's node count), as are tree ids without nodes.
+ * Refused, with *status bit 0 set and the tree's outputs left unwritten: a second incoming edge
+ * on a node (also BGCN_STATUS_TWO_PARENTS), an edge that leaves its tree (also
+ * BGCN_STATUS_CROSS_TREE; both trees), a cycle (also BGCN_STATUS_CYCLE), an endpoint outside
+ * [0, N) (the other endpoint's tree).  A batch vector that decreases, or holds an id outside
+ * [0, B), sets bit 0 and nothing is written.
+ *
+ * bgcn_rank_similarity: orders int32 [num_lists, num_nodes] (row stride ld) are rankings as
+ * bgcn_segment_rank writes them (per tree: local node indices, best first); num_lists in [1, 32]
+ * and k in [2, 32] (BGCN_RANK_SIMILARITY_MAX), else BGCN_EINVAL; at most 2^26 nodes (the sums are
+ * exact in int64).  sim fp64 [B, 5, num_lists, num_lists], valid int32 [B].  A tree of n <= k nodes
+ * gets zeros and valid 0 (the reference's `continue`).  Otherwise valid is 1 and for lists i, j,
+ * x and y their first k entries:
+ *   0 Pearson r of x and y as numbers     1 Spearman rho (Pearson of the entries' ranks inside
+ *   their list)     2 Kendall tau     3 Somers' D     4 Jaccard of the two index sets.
+ * The lists hold k distinct indices, so no ties: tau-b = tau-a = D.  Every sum is an exact int64;
+ * each value is one fp64 division (after one sqrt for 0 and 1), so 2-4 are exact rationals
+ * rounded once and the matrix is symmetric bit for bit.  A list that repeats an index, or holds
+ * one outside [0, n), inside its first k is not a ranking: *status bit 1 is set, the tree's block
+ * is NaN and valid 0.  One workgroup per tree.  Deterministic.
+ * -------------------------------------------------------------------------- */
+#define BGCN_TREE_CENTRALITY_LDS 2048
+#define BGCN_RANK_SIMILARITY_MAX 32
+#define BGCN_STATUS_TWO_PARENTS 32
+#define BGCN_STATUS_CYCLE 64
+size_t bgcn_tree_centrality_workspace_size(int64_t num_nodes, int64_t num_graphs);
+int bgcn_tree_centrality(const int64_t* edge_index, int64_t num_edges, const int64_t* batch,
+                         int64_t num_nodes, int64_t num_graphs, float* cent, int64_t ld, int32_t* status,
+                         void* workspace, size_t workspace_bytes, bgcn_stream_t stream);
+size_t bgcn_rank_similarity_workspace_size(int64_t num_graphs);
+int bgcn_rank_similarity(const int32_t* orders, int64_t ld, int64_t num_lists, const int64_t* batch,
+                         int64_t num_nodes, int64_t num_graphs, int32_t k, double* sim, int32_t* valid,
+                         int32_t* status, void* workspace, size_t workspace_bytes, bgcn_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * DropEdge (Process/dataset.py:68-90): per tree, keep a uniform random subset of
  * exactly int(E_t * (1 - droprate)) edges (count computed in double as Python does),
  * in their original order; droprate <= 0 keeps every edge (the reference's
