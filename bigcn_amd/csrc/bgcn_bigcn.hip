@@ -940,9 +940,10 @@ static bool dense_launched(const bgcn_bigcn_args* a, const SparseState& sp) {
 // propagate, conv2, propagate, readout.  When a backward follows, the CSC of X for dW1
 // is built on the auxiliary lane right after conv1's lin, overlapped with the
 // latency-bound second half of the forward, and joined before returning.  graph_lane
-// >= 0: the caller is building the TD/BU graphs on that lane (bgcn_train_step), joined
-// just before their first use.  head (bgcn_train_step): classifier head fused into the
-// readout.
+// >= 0 (a prepared batch only): bgcn_train_step queued the dense path's preparation of this
+// very batch on that lane beside conv1's GEMM; joined after the GEMM, before the first use of
+// the graphs, the tree maps and the batch status.  head (bgcn_train_step): classifier head
+// fused into the readout.
 static int forward_tail(const bgcn_bigcn_args* a, FusedWs& w, SparseState& sp, KeepSrc keep,
                         const int32_t* gate, hipStream_t s, const HeadArgs* head, bool forked);
 
@@ -976,19 +977,19 @@ int bigcn_forward_impl(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, hipS
     if (dense_launched(a, sp))
       BGCN_TRY(gemm_xwt_x(a->x, a->x_dtype, a->ldx, a->td_w1, a->bu_w1, F, H, w.z1, 2 * H, N, 2 * H,
                           F, s, gate));
-    if (graph_lane >= 0) BGCN_TRY(aux_join(s, graph_lane));   // K1 of a just-prepared batch
+    if (graph_lane >= 0) BGCN_TRY(aux_join(s, graph_lane));   // the preparation of a just-prepared batch
     return forward_tail(a, w, sp, keep, gate, s, head, false);
   }
 
   // one prologue launch: weight transposes, node -> root map, tree pointers, flag reset
   BGCN_TRY(sparse_prologue(sp, a, w.node_root, s));
   // tree work items (conv2 / dW2 root partials) on the side lane, beside the pass over X
-  bool side_busy = graph_lane >= 0;
+  bool side_busy = false;
   if (sparse) {
     hipStream_t xi;
     BGCN_TRY(aux_fork(s, kLaneSide, &xi));
     BGCN_TRY(sparse_items(sp, a->tree_ptr, a->rootindex, xi));
-    side_busy = side_busy || xi != s;
+    side_busy = xi != s;
   }
   // conv1 lin, TD and BU in one pass over X: sparse (compaction + gather) or dense MFMA
   // (the conv1 of feat_mode dense; in auto mode a device-gated fallback)
@@ -1004,8 +1005,8 @@ int bigcn_forward_impl(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, hipS
                         s, gate));
     timing_end(sparse ? 4 : 0, s);
   }
-  // the graphs (built on graph_lane by bgcn_train_step) and the items are needed from
-  // here on; the join comes before the CSC fork so that it never waits for the CSC
+  // the items are needed from here on; the join comes before the CSC fork so that it
+  // never waits for the CSC
   if (side_busy) BGCN_TRY(aux_join(s, kLaneSide));
   if (sparse && a->save_for_backward) {
     hipStream_t x;

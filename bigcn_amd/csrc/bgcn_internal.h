@@ -388,7 +388,7 @@ __device__ inline void head_grad_block(const HeadGradJob& j, int hb, float* sm) 
   }
 }
 
-// ---- fused encoder (bgcn_bigcn.hip); graph_lane: see bigcn_forward_impl
+// ---- fused encoder (bgcn_bigcn.hip); graph_lane (with prep only): see bigcn_forward_impl
 size_t bigcn_ws_size(int64_t N, int64_t B, int64_t F, int64_t hid);
 struct Prepared;
 struct WeightImages;

@@ -85,12 +85,6 @@ struct Prepared;
 // preparation and the fused encoder's setup both bind through it); flags / nnz / cols /
 // vals, root_map and bstatus differ between the two and stay with the callers.
 void bind_prepared(const Prepared& p, SparseState& S);
-// weight-independent preparation of one batch into p as separate launches on `s` (a step
-// that prepares its own batch beside K1 on another lane): node maps, tree items, the ELL
-// of X (the pass over X), then the CSC of X
-int sparse_prepare(const Prepared& p, int64_t N, int64_t B, int64_t F, int mode,
-                   const int64_t* batch, const int64_t* rootindex, const void* X, int xdt, int64_t ldx,
-                   hipStream_t s, const bgcn_batch* csr = nullptr);
 int sparse_conv1_gather(SparseState& S, float* Z1, hipStream_t s);
 int sparse_compact_conv1(SparseState& S, const void* X, int xdt, int64_t ldx, float* Z1,
                          hipStream_t s);
@@ -138,7 +132,7 @@ struct BwdTailArgs {
   SparseState S;
   const float* dZ1;
   float *dw1_td, *dw1_bu;
-  int n_dw1, n_rootcols;         // (set by launcher)
+  int n_dw1;                     // (set by launcher)
   const int32_t* node_root;
   const int64_t* batch;
   float *dw2_td, *dw2_bu;
@@ -154,11 +148,13 @@ struct BwdTailArgs {
 int bwd_mid_launch(BwdMidArgs& a, int x_dtype, hipStream_t s);
 int dw2_bf16_launch(BwdMidArgs& a, hipStream_t s);   // dense mode: dW2 root columns (bf16 MFMA)
 int dw2_f32_launch(BwdMidArgs& a, hipStream_t s);    // dense mode, fp32 X: dW2 (k_dw2_f32)
-// the whole weight-independent preparation of one batch on one stream (six launches;
-// mode 1 = dense: no ELL / CSC of X); nlanes: 1 = every launch on `s`, 2 = DropEdge + K1
+// the whole weight-independent preparation of one batch, queued on `s` (six launches;
+// mode 1 = dense: no ELL / CSC of X).  paced: the pass over X runs beside a training chain
+// and takes a capped grid (a step's own batch with nothing beside it: the full grid;
+// BGCN_PREP_BLOCKS overrides either).  nlanes: 1 = every launch on `s`, 2 = DropEdge + K1
 // forked onto the graph lane beside the pass over X, 0 = the default (BGCN_PREP_LANES)
 int prep_pipeline(const Prepared& p, const bgcn_batch* b, int64_t F, int degree_on, int mode,
-                  hipStream_t s, bool x_part = true, int nlanes = 0);
+                  hipStream_t s, bool paced, int nlanes = 0);
 // part: 0 = the whole tail; 1 = all but dW1; 2 = dW1 only (the deferred-dW1 step)
 int bwd_tail_launch(BwdTailArgs& a, hipStream_t s, int part = 0);
 

@@ -485,11 +485,6 @@ __device__ inline void csr_ell_body(const SparseState& S, const int32_t* __restr
   }
 }
 
-__global__ __launch_bounds__(256) void k_csr_ell(SparseState S, const int32_t* __restrict__ rp,
-                                                 const int32_t* __restrict__ rc, const float* __restrict__ rv) {
-  csr_ell_body(S, rp, rc, rv, int(blockIdx.x), int(gridDim.x));
-}
-
 // bgcn_csr_to_dense: one wave per row, the row assembled in LDS (zeros, then the row's
 // entries) and written with 16-byte stores - every output element written once, in order.
 template <class TX>
@@ -529,10 +524,11 @@ __global__ __launch_bounds__(128) void k_csr_dense(const int32_t* __restrict__ r
   }
 }
 
-template <bool kConv1, class TX>
+// the per-op encoder's forward: compaction + conv1 in one pass over X
+template <class TX>
 __global__ __launch_bounds__(256) void k_compact_conv1(SparseState S, const TX* __restrict__ X,
                                                        int64_t ldx, float* __restrict__ Z1) {
-  compact_body<kConv1, TX>(S, X, ldx, Z1, int(blockIdx.x), int(gridDim.x));
+  compact_body<true, TX>(S, X, ldx, Z1, int(blockIdx.x), int(gridDim.x));
 }
 
 // conv1 lin from a prepared ELL of X (bgcn_prepare_batch), the 128 outputs of both
@@ -1776,7 +1772,7 @@ __device__ inline void prep_b_body(const PrepArgs& a) {
 #define BGCN_PREP_B_WAVES 2
 #endif
 template <class TX>
-__global__ __launch_bounds__(256, BGCN_PREP_B_WAVES) void k_prep_b(PrepArgs a) {
+__device__ __forceinline__ void prep_b_stamped(const PrepArgs& a) {
   if (a.span && threadIdx.x == 0 && blockIdx.x < kSpanStarts)
     a.span[blockIdx.x] = uint64_t(wall_clock64());
   prep_b_body<TX>(a);
@@ -1786,6 +1782,20 @@ __global__ __launch_bounds__(256, BGCN_PREP_B_WAVES) void k_prep_b(PrepArgs a) {
       atomicMax(reinterpret_cast<unsigned long long*>(a.span) + kSpanStarts + blockIdx.x % kSpanEnds,
                 static_cast<unsigned long long>(wall_clock64()));
   }
+}
+
+template <class TX>
+__global__ __launch_bounds__(256, BGCN_PREP_B_WAVES) void k_prep_b(PrepArgs a) {
+  prep_b_stamped<TX>(a);
+}
+
+// The unpaced pass (a step's own batch with nothing to prefetch: the full grid, no chain
+// beside it) is bound by its own occupancy instead: three waves per SIMD (168 VGPRs, no
+// spills) drain fp32 X in 0.099 ms at Twitter15 size against 0.108 ms with two
+// (profiles/prep_one_path_ab.txt).  bf16 X takes 128 registers either way.
+template <class TX>
+__global__ __launch_bounds__(256, 3) void k_prep_b_alone(PrepArgs a) {
+  prep_b_stamped<TX>(a);
 }
 
 // The graph lane's launches of the two-lane preparation carry only their K1 / DropEdge
@@ -2067,7 +2077,6 @@ int bwd_tail_launch(BwdTailArgs& a, hipStream_t s, int part) {
   const int cols1 = split == 4 ? wpb / 4 : wpb;
   a.n_dw1 = !sparse ? 0 : split == 0 ? dw1_sliced_blocks(a.S.F, wpb) : int((a.S.F + cols1 - 1) / cols1);
   if (part == 1) a.n_dw1 = !sparse ? 0 : int((a.S.F + wpb - 1) / wpb);   // root columns: a wave per column
-  a.n_rootcols = 0;   // the dW2 root columns ride with the dW1 waves (dw1_body)
   // the reduction configurations are sized in 1024-thread blocks (4 groups of 256)
   a.red_dense.blocks *= 1024 / kTailThreads;
   a.red_sparse.blocks *= 1024 / kTailThreads;
@@ -2168,10 +2177,10 @@ int sparse_prologue(SparseState& S, const bgcn_bigcn_args* a, int32_t* node_root
 int sparse_compact_conv1(SparseState& S, const void* X, int xdt, int64_t ldx, float* Z1,
                          hipStream_t s) {
   if (xdt == BGCN_DTYPE_BF16)
-    hipLaunchKernelGGL((k_compact_conv1<true, bf16_t>), dim3(grid_for(S.N, 4)), dim3(256), 0, s, S,
+    hipLaunchKernelGGL(k_compact_conv1<bf16_t>, dim3(grid_for(S.N, 4)), dim3(256), 0, s, S,
                        static_cast<const bf16_t*>(X), ldx, Z1);
   else
-    hipLaunchKernelGGL((k_compact_conv1<true, float>), dim3(grid_for(S.N, 4)), dim3(256), 0, s, S,
+    hipLaunchKernelGGL(k_compact_conv1<float>, dim3(grid_for(S.N, 4)), dim3(256), 0, s, S,
                        static_cast<const float*>(X), ldx, Z1);
   BGCN_CHECK_LAUNCH();
   return BGCN_OK;
@@ -2225,7 +2234,7 @@ static void prepared_state(const Prepared& p, int64_t N, int64_t B, int64_t F, i
 }
 
 int prep_pipeline(const Prepared& p, const bgcn_batch* bt, int64_t F, int degree_on, int mode,
-                  hipStream_t s, bool x_part, int nlanes) {
+                  hipStream_t s, bool paced, int nlanes) {
   const int64_t N = bt->num_nodes, B = bt->num_graphs;
   BGCN_CHECK_HIP(hipMemsetAsync(p.status, 0, sizeof(int32_t), s));
   PrepArgs a{};
@@ -2261,8 +2270,7 @@ int prep_pipeline(const Prepared& p, const bgcn_batch* bt, int64_t F, int degree
     a.nzero[k] = int(zb[k] / 16);
     BGCN_CHECK_ARG(zb[k] % 16 == 0 && (reinterpret_cast<uintptr_t>(a.zero[k]) & 15) == 0, "zero range");
   }
-  const bool sparse = mode != 1;
-  const bool xp = sparse && x_part;   // the pass over X and the CSC of X in these launches
+  const bool xp = mode != 1;   // the pass over X and the CSC of X in these launches
   const int64_t Emax = std::max(Etd, Ebu);
   a.nz = int((a.nzero[0] + a.nzero[1] + 255) / 256);
   a.nR = int((N + 255) / 256);
@@ -2280,7 +2288,9 @@ int prep_pipeline(const Prepared& p, const bgcn_batch* bt, int64_t F, int degree
       // (profiles/r02_pace_ab.txt).  bf16 X (the prefix compaction, compact_by_prefix):
       // one block per CU - 192 / 256 / 320 / 512 / 1024 blocks / the full grid: weibo_bf16
       // 0.667 / 0.646 / 0.661 / 0.709 / 0.688 / 0.697 ms (profiles/r02_compact_ab.txt).
-      // BGCN_PREP_BLOCKS (read per call) overrides: 0 = full grid, n = n blocks.
+      // Not paced (a step's own batch with nothing to prefetch: no chain runs beside the
+      // pass): the full grid.  BGCN_PREP_BLOCKS (read per call) overrides either: 0 = full
+      // grid, n = n blocks.
     static const int ncu = [] {
       int dev = 0, n = 0;
       if (hipGetDevice(&dev) != hipSuccess ||
@@ -2290,7 +2300,8 @@ int prep_pipeline(const Prepared& p, const bgcn_batch* bt, int64_t F, int degree
     }();
     const bool bf = bt->x_dtype == BGCN_DTYPE_BF16;
     a.ncomp = xp ? int(grid_for(N, bf ? 8 : 4)) : 0;
-    const int cap = int(knob("BGCN_PREP_BLOCKS", bf ? (compact_by_prefix<bf16_t>() ? ncu : 0) : ncu + ncu / 2));
+    const int paced_cap = bf ? (compact_by_prefix<bf16_t>() ? ncu : 0) : ncu + ncu / 2;
+    const int cap = int(knob("BGCN_PREP_BLOCKS", paced ? paced_cap : 0));
     if (cap > 0) a.ncomp = std::min(a.ncomp, cap);
     // host-fed compacted rows: 8 rows per block over every row, nothing to pace (nnz x 8 B)
     if (a.xr_ptr && xp) a.ncomp = int(grid_for(N, 8));
@@ -2303,6 +2314,9 @@ int prep_pipeline(const Prepared& p, const bgcn_batch* bt, int64_t F, int degree
   a.nn = graph_node_blocks(N);
   a.np = graph_pos_blocks(Emax, N);
   const dim3 blk(256);
+  const bool bf16 = bt->x_dtype == BGCN_DTYPE_BF16;
+  void (*const prep_b)(PrepArgs) = paced ? (bf16 ? k_prep_b<bf16_t> : k_prep_b<float>)
+                                         : (bf16 ? k_prep_b_alone<bf16_t> : k_prep_b_alone<float>);
   hipLaunchKernelGGL(k_prep_a, dim3(unsigned(a.nz + a.nRP + a.nbd[0] + a.nbd[1])), blk, 0, s, a);
   BGCN_CHECK_LAUNCH();
   const size_t hist_smem = xp ? size_t(F) * sizeof(int32_t) : 0;
@@ -2333,8 +2347,7 @@ int prep_pipeline(const Prepared& p, const bgcn_batch* bt, int64_t F, int degree
     BGCN_CHECK_LAUNCH();
     timing_begin(7, s);
     ax.span = span_slot(7);
-    if (bt->x_dtype == BGCN_DTYPE_BF16) hipLaunchKernelGGL(k_prep_b<bf16_t>, dim3(unsigned(1 + ax.ncomp)), blk, 0, s, ax);
-    else hipLaunchKernelGGL(k_prep_b<float>, dim3(unsigned(1 + ax.ncomp)), blk, 0, s, ax);
+    hipLaunchKernelGGL(prep_b, dim3(unsigned(1 + ax.ncomp)), blk, 0, s, ax);
     BGCN_CHECK_LAUNCH();
     timing_end(7, s);
     hipLaunchKernelGGL(k_prep_c, dim3(unsigned(ax.R)), blk, hist_smem, s, ax);
@@ -2347,9 +2360,7 @@ int prep_pipeline(const Prepared& p, const bgcn_batch* bt, int64_t F, int degree
   }
   timing_begin(7, s);
   a.span = span_slot(7);
-  const unsigned nb = unsigned(a.nsel + 1 + a.ncomp);
-  if (bt->x_dtype == BGCN_DTYPE_BF16) hipLaunchKernelGGL(k_prep_b<bf16_t>, dim3(nb), blk, 0, s, a);
-  else hipLaunchKernelGGL(k_prep_b<float>, dim3(nb), blk, 0, s, a);
+  hipLaunchKernelGGL(prep_b, dim3(unsigned(a.nsel + 1 + a.ncomp)), blk, 0, s, a);
   BGCN_CHECK_LAUNCH();
   timing_end(7, s);
   if (2 * a.nce + a.R > 0) {
@@ -2363,32 +2374,6 @@ int prep_pipeline(const Prepared& p, const bgcn_batch* bt, int64_t F, int degree
   hipLaunchKernelGGL(k_prep_f, dim3(unsigned(2 * (a.ne + a.nn + a.np) + a.R)), blk, 2 * hist_smem, s, a);
   BGCN_CHECK_LAUNCH();
   return BGCN_OK;
-}
-
-int sparse_prepare(const Prepared& p, int64_t N, int64_t B, int64_t F, int mode,
-                   const int64_t* batch, const int64_t* rootindex, const void* X, int xdt, int64_t ldx,
-                   hipStream_t s, const bgcn_batch* csr) {
-  SparseState S{};
-  prepared_state(p, N, B, F, mode, S);
-  const int nR = int((N + 255) / 256), nP = int((B + 1 + 255) / 256);
-  hipLaunchKernelGGL(k_prologue, dim3(unsigned(nR + nP)), dim3(256), 0, s, S, nullptr, nullptr,
-                     nullptr, nullptr, batch, rootindex, p.node_root, p.tree_ptr, 1, 0, nR);
-  BGCN_CHECK_LAUNCH();
-  if (mode == 1) return BGCN_OK;
-  BGCN_TRY(sparse_items(S, p.tree_ptr, rootindex, s));
-  timing_begin(7, s);
-  const dim3 grid(grid_for(N, xdt == BGCN_DTYPE_BF16 ? 8 : 4));
-  if (!X && csr)
-    hipLaunchKernelGGL(k_csr_ell, dim3(grid_for(N, 8)), dim3(256), 0, s, S, csr->x_row_ptr, csr->x_col, csr->x_val);
-  else if (xdt == BGCN_DTYPE_BF16)
-    hipLaunchKernelGGL((k_compact_conv1<false, bf16_t>), grid, dim3(256), 0, s, S,
-                       static_cast<const bf16_t*>(X), ldx, nullptr);
-  else
-    hipLaunchKernelGGL((k_compact_conv1<false, float>), grid, dim3(256), 0, s, S,
-                       static_cast<const float*>(X), ldx, nullptr);
-  timing_end(7, s);
-  BGCN_CHECK_LAUNCH();
-  return sparse_csc(S, s);
 }
 
 int sparse_conv1_gather(SparseState& S, float* Z1, hipStream_t s) {

@@ -169,41 +169,21 @@ static int carve_batch(const bgcn_batch& b, int64_t F, void* buf, size_t bytes, 
   return BGCN_OK;
 }
 
-// gs: stream of the graph build (K1); the caller joins it before the graphs are used
+// prep_pipeline's mode of a batch: 1 = the dense feature path (no ELL / CSC of X), else 0
+static int prep_mode(int feat_mode, int64_t F, int64_t N) {
+  return (feat_mode == BGCN_FEAT_DENSE || F > kSparseMaxFeat || N > kSparseMaxN) ? 1 : 0;
+}
+
+// The weight-independent preparation of one batch into its prepared buffer, queued on `s`:
+// the merged launches of prep_pipeline (bgcn_sparse.hip; paced, lanes: as there)
 static int prepare_into(const bgcn_batch* b, int64_t F, int degree_on, int feat_mode, void* buf,
-                        size_t bytes, hipStream_t s, Prepared* out, hipStream_t gs, int lanes = 0) {
+                        size_t bytes, hipStream_t s, Prepared* out, bool paced, int lanes = 0) {
   BGCN_TRY(check_batch(b));
   BGCN_CHECK_ARG(F > 0 && F % 4 == 0 && b->ldx >= F && b->ldx % 4 == 0, "bad in_feats / ldx");
-  const int64_t N = b->num_nodes, B = b->num_graphs;
   Prepared p;
   BGCN_TRY(carve_batch(*b, F, buf, bytes, &p));
   BGCN_TRY(check_feat_input(b, feat_mode, F));
-  const int mode = (feat_mode == BGCN_FEAT_DENSE || F > kSparseMaxFeat || N > kSparseMaxN) ? 1 : 0;
-  // one stream: the six merged launches (DropEdge, K1, the pass over X and the CSC of X
-  // side by side, bgcn_sparse.hip prep_pipeline)
-  if (s == gs) {
-    BGCN_TRY(prep_pipeline(p, b, F, degree_on, mode, s, true, lanes));
-    if (out) *out = p;
-    return BGCN_OK;
-  }
-  // the graph build on its own stream (a step that prepares its own batch with nothing to
-  // prefetch): DropEdge and K1 on gs, the pass over X and the CSC as separate launches on s
-  BGCN_CHECK_HIP(hipMemsetAsync(p.status, 0, sizeof(int32_t), gs));
-  const int64_t* td = b->td_edge_index;
-  const int64_t* bu = b->bu_edge_index;
-  if (b->td_droprate > 0.0 || b->bu_droprate > 0.0) {
-    // DropEdge (dataset.py:68-90) in the masked form: dropped edges become self loops,
-    // which K1 removes - same graphs as the compacted lists, no kept count on the host
-    BGCN_TRY(drop_edges_impl(td, b->td_num_edges, p.td_drop, b->td_num_edges, b->td_droprate, bu,
-                             b->bu_num_edges, p.bu_drop, b->bu_num_edges, b->bu_droprate, b->batch,
-                             N, B, b->drop_seed, 1, nullptr, p.status, p.dws, p.dws_bytes, gs));
-    if (td) td = p.td_drop;
-    if (bu) bu = p.bu_drop;
-  }
-  BGCN_TRY(bgcn_build_graph_pair(td, b->td_num_edges, bu, b->bu_num_edges, N, degree_on, &p.td,
-                                 &p.bu, b->batch, p.status, p.gws, p.gws_bytes,
-                                 reinterpret_cast<bgcn_stream_t>(gs)));
-  BGCN_TRY(sparse_prepare(p, N, B, F, mode, b->batch, b->rootindex, b->x, b->x_dtype, b->ldx, s, b));
+  BGCN_TRY(prep_pipeline(p, b, F, degree_on, prep_mode(feat_mode, F, b->num_nodes), s, paced, lanes));
   if (out) *out = p;
   return BGCN_OK;
 }
@@ -254,7 +234,7 @@ struct Step {
   WeightImages im{};
   const WeightImages* img = nullptr;   // &im, or nullptr without an image buffer
   bgcn_bigcn_args e;
-  int graph_lane = -1;                 // the lane that builds a just-prepared batch's graphs
+  int graph_lane = -1;                 // the lane a just-prepared batch's preparation runs on (dense path)
 };
 
 // The argument checks the step entry points share, in the one order all of them report:
@@ -303,13 +283,19 @@ static int step_prepare(const bgcn_step_args* a, hipStream_t s, bool timed, Step
     timing_begin(9, s);
   }
   if (!a->prepared_ready) {
-    // prepare the current batch first; without a next batch to prefetch, its K1 runs on
-    // the side lane beside the pass over X (joined before the first propagate)
+    // prepare the current batch first.  With nothing to prefetch nothing runs beside its
+    // pass over X, which then takes the full grid (unpaced); K1 runs beside the pass on
+    // prep_pipeline's graph lane.  The dense feature path has no pass to hide K1 behind:
+    // its whole preparation goes to the side lane beside conv1's GEMM, and the forward
+    // joins it before the first propagate (st->graph_lane)
+    const bool alone = !a->next;
     hipStream_t g = s;
-    if (!a->next) BGCN_TRY(aux_fork(s, kLaneSide, &g));
-    BGCN_TRY(prepare_into(&a->cur, F, a->degree_on, a->feat_mode, a->prepared, a->prepared_bytes, s,
-                          &st->p, g));
-    if (g != s) st->graph_lane = kLaneSide;
+    if (alone && prep_mode(a->feat_mode, F, a->cur.num_nodes) == 1) {
+      BGCN_TRY(aux_fork(s, kLaneSide, &g));
+      if (g != s) st->graph_lane = kLaneSide;
+    }
+    BGCN_TRY(prepare_into(&a->cur, F, a->degree_on, a->feat_mode, a->prepared, a->prepared_bytes, g,
+                          &st->p, !alone, g != s ? 1 : 0));
   } else {
     BGCN_TRY(carve_batch(a->cur, F, a->prepared, a->prepared_bytes, &st->p));
   }
@@ -320,7 +306,7 @@ static int step_prepare(const bgcn_step_args* a, hipStream_t s, bool timed, Step
     BGCN_TRY(aux_fork(s, kLaneSide, &x));
     if (timed) timing_begin(8, x);
     BGCN_TRY(prepare_into(a->next, F, a->degree_on, a->feat_mode, a->next_prepared,
-                          a->next_prepared_bytes, x, nullptr, x));
+                          a->next_prepared_bytes, x, nullptr, true));
     if (timed) timing_end(8, x);
     // waited for by the next call, not joined by this one: the step's chain ends without a
     // cross-stream wait (chain alone 197 -> 190 us; beside a preparation the join was
@@ -458,7 +444,7 @@ extern "C" int bgcn_prepare_batch(const bgcn_batch* batch, int64_t in_feats, int
   // feed.prepare_ahead's side stream beside a host-bound per-op loop); forking the graph
   // build onto a second lane cost that caller's thread ~40 us of host time per batch
   // (two event records and waits) for no gain it could see (profiles/r06_prep_lanes_dropin.txt)
-  return bgcn::prepare_into(batch, in_feats, degree_on, feat_mode, prepared, prepared_bytes, s, nullptr, s, 1);
+  return bgcn::prepare_into(batch, in_feats, degree_on, feat_mode, prepared, prepared_bytes, s, nullptr, true, 1);
 }
 
 extern "C" size_t bgcn_train_step_workspace_size(int64_t num_nodes, int64_t num_graphs,

@@ -148,22 +148,77 @@ def test_train_step_reports_bad_inputs():
         step.check_status()
 
 
-@pytest.mark.parametrize("mode", ["auto", "sparse", "dense"])
+def _ragged_batch(seed, F=5000):
+    """~20 trees whose node count is no multiple of 8 (the last block of a full-grid pass
+    over X is ragged), one of them a single node, and one feature row over the ELL cap (the
+    spill pool and the long-row list are filled); the host hints are refreshed."""
+    from bigcn_amd.data import synth_batch, synth_tree_sizes
+    rng = np.random.default_rng(seed)
+    sizes = synth_tree_sizes(rng, 20, 150)
+    sizes[7] = 1
+    sizes[-1] += (3 - int(sizes.sum())) % 8                # N = 3 (mod 8)
+    b = synth_batch(rng, sizes, F, 4, 0.2, 0.2, device=DEV)
+    N = b.x.size(0)
+    assert N % 8 == 3 and int((b.batch == 7).sum()) == 1
+    g = torch.Generator().manual_seed(seed)
+    row = torch.zeros(F)
+    row[torch.randperm(F, generator=g)[:40]] = torch.randint(1, 4, (40,), generator=g).float()
+    b.x[N // 2] = row.to(DEV)
+    nnz = (b.x != 0).sum(1)
+    assert int(nnz.max()) == 40
+    b.set_x_nnz_max(int(nnz.max()), int((nnz - 32).clamp_min(0).sum()))
+    return b
+
+
+def _prefetch_case(case):
+    """(batches, in_feats, feat_mode, FusedTrainStep keywords) of a case of
+    test_next_batch_prefetch_matches_plain_steps."""
+    mode, _, kind = case.partition("-")
+    F = 768 if mode == "dense" else 5000
+    kw = {}
+    if kind == "csr":        # host-fed: the features arrive as the CSR of their non-zeros (x == NULL)
+        from bigcn_amd import feed as FD
+        store = FD.TreeStore.synthetic(60, 150, seed=43, in_feats=F, root_random=True)
+        batches = []
+        for k in range(3):
+            hb = FD.pack_batch(store, list(range(20 * k, 20 * k + 20)))
+            batches.append(FD.PackedBatch(hb.buf.to(DEV), hb.meta, hb.root_tweetids, None, torch.float32))
+        assert all(b.fits_sparse for b in batches)
+    elif kind == "ragged":
+        batches = [_ragged_batch(50 + k, F) for k in range(3)]
+    elif kind == "drop":     # DropEdge drawn on the device by each preparation: undropped batches
+        batches = [_synth(40 + k, 20, 150, F=F, droprates=(0.0, 0.0)) for k in range(3)]
+        kw = dict(tddroprate=0.2, budroprate=0.3, drop_seed=4711)
+    elif kind == "bf16":     # (a replaced x drops the host hint: "auto" is the device-gated form)
+        batches = [_synth(40 + k, 20, 150, F=F) for k in range(3)]
+        for b in batches:
+            b.x = b.x.to(torch.bfloat16)
+    else:
+        assert kind == ""
+        batches = [_synth(40 + k, 24, 150) for k in range(3)]
+        F = 5000
+    return batches, F, mode, kw
+
+
+@pytest.mark.parametrize("mode", ["auto", "sparse", "dense", "auto-bf16", "sparse-bf16", "sparse-csr",
+                                  "sparse-ragged", "auto-drop", "dense-drop"])
 def test_next_batch_prefetch_matches_plain_steps(mode):
     """Preparing the next batch inside a step (side lane) gives bitwise the same losses and
     gradients as preparing every batch inside its own step; a prefetched buffer is only
-    used when the next call trains on that very batch."""
+    used when the next call trains on that very batch.  A step's own batch takes the same
+    preparation launches, its pass over X on the full grid: bf16 X, host-fed CSR rows, a
+    ragged last block with a spilled row and device DropEdge go through it as well."""
     from bigcn_amd import FusedTrainStep
-    batches = [_synth(40 + k, 24, 150) for k in range(3)]
-    p = O.make_params(5000, 64, 64, 4, seed=17)
+    batches, F, mode, kw = _prefetch_case(mode)
+    p = O.make_params(F, 64, 64, 4, seed=17)
     ref, got = [], []
     m1 = _model(p, mode)
-    s1 = FusedTrainStep(m1)
+    s1 = FusedTrainStep(m1, **kw)
     for k, b in enumerate(batches):
         loss = s1.forward_backward(b, seed=k)
         ref.append((loss.clone(), [v.clone() for v in s1.grads().values()]))
     m2 = _model(p, mode)
-    s2 = FusedTrainStep(m2)
+    s2 = FusedTrainStep(m2, **kw)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):                       # non-default stream: real side lane
@@ -173,7 +228,11 @@ def test_next_batch_prefetch_matches_plain_steps(mode):
             got.append((loss.clone(), [v.clone() for v in s2.grads().values()]))
         # a prefetched batch that is not the next one trained on is ignored
         s2.forward_backward(batches[0], seed=9, next_data=batches[1])
+        # (the two calls above drew DropEdge seeds of their own: the last step draws the one
+        # the plain run's third step drew)
+        s2._drop_count = 2
         loss = s2.forward_backward(batches[2], seed=2)
+        assert s2.last_drop_seed == s1.last_drop_seed
         got_last = [v.clone() for v in s2.grads().values()]
     torch.cuda.synchronize()
     for (l1, g1), (l2, g2) in zip(ref, got):
