@@ -12,6 +12,10 @@ Drop-in symbols for the reference's hot path (cwkd/BiGCN):
 * ``compare`` / ``tree_centrality`` / ``rank_similarity`` - the reference's comparison
   (compare_similarity.py): the trees' graph centralities and, per tree, five similarity statistics of
   every pair of rankings
+* ``metrics`` - the reference's evaluation metrics (tools/evaluate.py): ``confusion`` counts labels against
+  predictions on the device, ``class_metrics`` / ``evaluation4class`` / ``evaluationclass`` give the
+  reference's numbers from the counts, ``EpochMetrics`` records a validation epoch without a host sync
+  (``FusedTrainStep.validate`` is the reference's test loop around it)
 * ``FusedTrainStep`` - the training-loop body (BiGCN_Twitter.py:183-189) as one native call
   + the data-parallel all-reduce + fused Adam
 
@@ -22,6 +26,8 @@ from .conv import GCNConv
 from .compare import compare, rank_similarity, tree_centrality
 from .ebgcn import EBGCN
 from .explain import explain, segment_rank
+from . import metrics
+from .metrics import EpochMetrics, class_metrics, confusion, evaluation4class, evaluationclass
 from .ops import Graph, bigcn_encoder, build_graph, edge_infer, gcn_conv, scatter_mean, spmm
 from .optim import FusedAdam, bigcn_adam
 from .train import FusedTrainStep
@@ -29,5 +35,6 @@ from .train import FusedTrainStep
 __all__ = ["GCNConv", "scatter_mean", "TDrumorGCN", "BUrumorGCN", "BiGCN", "Net", "make_optimizer",
            "Graph", "build_graph", "gcn_conv", "spmm", "bigcn_encoder", "FusedAdam", "bigcn_adam",
            "FusedTrainStep", "EBGCN", "edge_infer", "explain", "segment_rank",
-           "compare", "tree_centrality", "rank_similarity"]
+           "compare", "tree_centrality", "rank_similarity",
+           "metrics", "confusion", "class_metrics", "evaluation4class", "evaluationclass", "EpochMetrics"]
 __version__ = "0.1.0"

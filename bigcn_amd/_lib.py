@@ -63,7 +63,7 @@ EXPORTED_SYMBOLS = (
     "bgcn_bn_fold", "bgcn_edge_infer", "bgcn_ebgcn_conv2_lin_workspace_size", "bgcn_ebgcn_conv2_lin",
     "bgcn_explain_sums_workspace_size", "bgcn_explain_sums", "bgcn_segment_rank_workspace_size", "bgcn_segment_rank",
     "bgcn_tree_centrality_workspace_size", "bgcn_tree_centrality", "bgcn_rank_similarity_workspace_size",
-    "bgcn_rank_similarity",
+    "bgcn_rank_similarity", "bgcn_confusion",
 )
 
 
@@ -231,6 +231,7 @@ _SIGS = {
     "bgcn_rank_similarity_workspace_size": (c_size_t, [c_int64]),
     "bgcn_rank_similarity": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "bgcn_confusion": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

@@ -117,7 +117,7 @@ def explain_direction(direction_module, data, batch_of_one: bool = False) -> Dir
 class Explanation:
     """What :func:`explain` returns for one batch.  ``x_sum`` [N], ``x_order`` / ``x_sorted`` [N]
     (its per-tree ranking), ``td`` / ``bu`` (:class:`DirectionExplanation`), ``log_probs`` [B, C]
-    of the model's normal forward, ``prediction`` [B]; ``batch`` / ``rootindex`` are the batch's."""
+    of the model's normal forward, ``prediction`` [B]; ``batch`` / ``rootindex`` / ``y`` are the batch's."""
     x_sum: torch.Tensor
     x_order: torch.Tensor
     x_sorted: torch.Tensor
@@ -128,6 +128,19 @@ class Explanation:
     batch: torch.Tensor
     rootindex: torch.Tensor
     _ptr: Optional[list] = None
+    y: Optional[torch.Tensor] = None   # the batch's labels [B] (None: the batch had none)
+
+    def confusion(self, num_classes: int = 4, out: Optional[torch.Tensor] = None,
+                  status: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``prediction`` counted against the batch's ``y`` on the device: the int32 ``[C, C]``
+        matrix (row = actual, column = predicted) the reference's explain run keeps per fold
+        (``explain_PHEME.py:480, 609``).  With ``out`` the counts are ADDED to it - one zeroed
+        buffer over a fold's batches gives the fold's matrix.  No host sync
+        (:func:`bigcn_amd.metrics.confusion`; a label outside ``[0, C)`` sets bit 0 of ``status``)."""
+        from .metrics import confusion
+        if self.y is None:
+            raise ValueError("the explained batch has no labels (y)")
+        return confusion(self.prediction, self.y, num_classes, out=out, accumulate=out is not None, status=status)
 
     def tree_ptr(self) -> list:
         """First node of every tree (B + 1 entries), on the host."""
@@ -182,4 +195,5 @@ def explain(model, data, batch_of_one: bool = False) -> Explanation:
         log_probs = out[0] if isinstance(out, tuple) else out     # EBGCN returns (log_probs, None, None)
         prediction = log_probs.argmax(dim=-1)
         _raise_on(status)
-    return Explanation(x_sum, x_order[0], x_sorted[0], td, bu, log_probs, prediction, data.batch, data.rootindex)
+    return Explanation(x_sum, x_order[0], x_sorted[0], td, bu, log_probs, prediction, data.batch, data.rootindex,
+                       y=getattr(data, "y", None))

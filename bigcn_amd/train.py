@@ -381,6 +381,30 @@ class FusedTrainStep:
         out = (loss.view(()), correct.view(()))
         return out + (pr,) if pred else out
 
+    def validate(self, batches, metrics=None):
+        """The reference's test loop (``BiGCN_Twitter.py:207-233``) as one call, without a host
+        sync: every batch goes through ``evaluate(batch, next_data=<the following batch>,
+        pred=True)`` and its loss, correct count, predictions and labels into
+        ``metrics.add(...)``.  ``metrics``: the :class:`bigcn_amd.metrics.EpochMetrics` to record
+        into (records are appended: ``reset()`` it between epochs); by default a new one sized
+        for ``batches``.  Returns it; ``result()`` is the epoch's one device-to-host read.
+        Validity of the batches themselves: ``check_status()`` / ``run_report()`` as for
+        ``evaluate``."""
+        from .metrics import EpochMetrics
+        batches = list(batches)
+        if metrics is None:
+            if not batches:
+                raise ValueError("validate needs at least one batch")
+            metrics = EpochMetrics(self.num_classes, len(batches), _device(batches[0]))
+        elif len(metrics) + len(batches) > metrics.max_batches:
+            raise IndexError(f"metrics has room for {metrics.max_batches - len(metrics)} more batches, "
+                             f"{len(batches)} given")
+        for k, batch in enumerate(batches):
+            nxt = batches[k + 1] if k + 1 < len(batches) else None
+            loss, correct, pred = self.evaluate(batch, next_data=nxt, pred=True)
+            metrics.add(pred, batch.y, loss, correct)
+        return metrics
+
     def finish_dw1(self) -> None:
         """The conv1 weight gradients of a step run with ``defer_dw1`` (bgcn_train_step_dw1:
         same arguments and buffers, on the current stream)."""

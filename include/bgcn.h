@@ -362,6 +362,19 @@ int bgcn_rank_similarity(const int32_t* orders, int64_t ld, int64_t num_lists, c
                          int32_t* status, void* workspace, size_t workspace_bytes, bgcn_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * The confusion matrix every number of the reference's validation loop derives from
+ * (tools/evaluate.py:3-139 called at BiGCN_Twitter.py:223; explain_PHEME.py:480,609 keeps the
+ * matrix itself): counts[a * C + p] = #{i : y[i] == a && pred[i] == p}, int32, row = actual,
+ * column = predicted.  pred, y: int64 [B], any B >= 0; num_classes C in [1, 16].
+ * One launch: accumulate == 0 overwrites all C * C bins (zeros for B == 0; no zeroing launch or
+ * memset is needed before the call), accumulate != 0 adds to them (B == 0: counts untouched).
+ * Integer arithmetic: exact and the same on every run.  An entry whose pred or y lies outside
+ * [0, C) is not counted and sets bit 0 of *status.  BGCN_EINVAL before any device work for a
+ * null pred, y, counts or status, num_classes outside [1, 16], B < 0. */
+int bgcn_confusion(const int64_t* pred, const int64_t* y, int64_t B, int num_classes, int32_t* counts,
+                   int accumulate, int32_t* status, bgcn_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * DropEdge (Process/dataset.py:68-90): per tree, keep a uniform random subset of
  * exactly int(E_t * (1 - droprate)) edges (count computed in double as Python does),
  * in their original order; droprate <= 0 keeps every edge (the reference's
