@@ -1244,7 +1244,7 @@ int bigcn_backward_impl(const bgcn_bigcn_args* a, void* ws, size_t ws_bytes, hip
   // with no dense kernel launched (the gated dense dW1 would arrive after the tail's blocks)
   if (adam && adam->on && sparse && !dense_launched(a, sp) && !defer_dw1) t.adam = *adam;
   BGCN_TRY(bwd_tail_launch(t, s, defer_dw1 ? 1 : 0));
-  // (the launcher clears adam.on for a tail form that cannot carry it: BGCN_DW1_SPLIT != 0)
+  // (adam.on is set only where the tail can carry it: not dense, not deferred)
   if (adam_done) *adam_done = t.adam.on != 0;
   timing_end(5, s);
   timing_end(9, s);   // the main stream's own chain (span class, bgcn_train_step)

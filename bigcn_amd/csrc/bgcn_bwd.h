@@ -1,4 +1,4 @@
-// Device bodies of the backward's middle and tail launches (bgcn_sparse.hip defines the
+// Device bodies of the backward's middle and tail launches (bgcn_sparse_bwd.hip defines the
 // merged kernels): the dW2 relu(H1)-block / dense partials, their fixed-order reduction
 // and dH1.  Each body takes its block id within its role and a slice of the launch's
 // shared memory, so several roles share one launch (one dependent launch instead of

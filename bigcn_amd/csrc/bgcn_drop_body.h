@@ -1,5 +1,5 @@
 // DropEdge device bodies (bgcn_drop.hip's standalone launches and the fused step's
-// batch preparation, bgcn_sparse.hip).  See bgcn_drop.hip for the algorithm.
+// batch preparation, bgcn_prep.hip).  See bgcn_drop.hip for the algorithm.
 #pragma once
 
 #include "bgcn_common.h"

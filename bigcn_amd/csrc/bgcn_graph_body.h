@@ -1,6 +1,6 @@
 // K1 device bodies (gcn_norm + add_remaining_self_loops + CSR, both orientations):
 // shared by the generic graph build (bgcn_graph.hip) and the fused step's batch
-// preparation, which runs them as roles of merged launches (bgcn_sparse.hip).
+// preparation, which runs them as roles of merged launches (bgcn_prep.hip).
 //
 // Unweighted graphs (every GCNConv of the BiGCN path) take four steps:
 //   count        per edge: target / source counts (int atomics), run starts

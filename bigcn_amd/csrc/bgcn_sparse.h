@@ -1,4 +1,5 @@
-// Sparse-feature path of the fused encoder (see bgcn_sparse.hip).
+// Sparse-feature path of the fused encoder (see bgcn_sparse.hip; the batch preparation:
+// bgcn_prep.hip; the backward's merged launches: bgcn_sparse_bwd.hip).
 #pragma once
 
 #include "bgcn_internal.h"
@@ -54,6 +55,7 @@ struct SparseState {
   const int32_t* root_map = nullptr;   // node -> its tree's root (the CSC placement flags root rows)
   int conv1_clears = 0;           // conv1's block 0 clears zero_word / rtick (no prologue launch)
 };
+__device__ __forceinline__ bool use_sparse(const SparseState& S) { return S.mode != 1 && S.flags[0] == 0; }
 // The weight images of the sparse path in a caller-owned persistent buffer
 // (bgcn_weight_images_size): kept current by bgcn_adam_step, so a step whose images are
 // current launches no prologue (its transposes and splits were the Adam's tile epilogue).
@@ -91,7 +93,7 @@ int sparse_compact_conv1(SparseState& S, const void* X, int xdt, int64_t ldx, fl
 int sparse_items(SparseState& S, const int32_t* tree_ptr, const int64_t* rootindex, hipStream_t s);
 int sparse_conv2(SparseState& S, const float* H1, float* Z2, KeepSrc keep, hipStream_t s);
 int sparse_csc(SparseState& S, hipStream_t s);
-// The backward's middle and tail launches (bgcn_sparse.hip): role block counts the
+// The backward's middle and tail launches (bgcn_sparse_bwd.hip): role block counts the
 // launchers fill in are marked (set by launcher).
 struct Dw2Cfg {
   int64_t kchunk;

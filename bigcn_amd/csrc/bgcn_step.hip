@@ -175,7 +175,7 @@ static int prep_mode(int feat_mode, int64_t F, int64_t N) {
 }
 
 // The weight-independent preparation of one batch into its prepared buffer, queued on `s`:
-// the merged launches of prep_pipeline (bgcn_sparse.hip; paced, lanes: as there)
+// the merged launches of prep_pipeline (bgcn_prep.hip; paced, lanes: as there)
 static int prepare_into(const bgcn_batch* b, int64_t F, int degree_on, int feat_mode, void* buf,
                         size_t bytes, hipStream_t s, Prepared* out, bool paced, int lanes = 0) {
   BGCN_TRY(check_batch(b));

@@ -519,29 +519,6 @@ def test_planned_and_merge_path_aggregation_match_oracle(plan, monkeypatch):
     step.check_status()
 
 
-def test_dw1_column_split_matches(monkeypatch):
-    """dW1 over the CSC of X by XCD-aware output slices (the default, "0"), with one wave
-    per column and with four waves per column: the same gradients up to summation order,
-    and every other gradient (the dW2 root columns included) bit for bit."""
-    from bigcn_amd import FusedTrainStep
-    b = _synth(48, 64, 200)
-    p = O.make_params(5000, 64, 64, 4, seed=29)
-    res = {}
-    for split in ("0", "1", "4"):
-        monkeypatch.setenv("BGCN_DW1_SPLIT", split)
-        step = FusedTrainStep(_model(p))
-        step.forward_backward(b, seed=3)
-        g = step.grads()
-        res[split] = {k: g[prm].clone() for k, prm in zip(KEYS, step.step_params)}
-    for k in KEYS:
-        if k.endswith("conv1.lin.weight"):
-            close(res["4"][k], res["1"][k], what=k)
-            close(res["0"][k], res["1"][k], what=k)
-        else:
-            assert torch.equal(res["1"][k], res["4"][k]), k
-            assert torch.equal(res["1"][k], res["0"][k]), k
-
-
 @pytest.mark.parametrize("mode", ["auto", "sparse"])
 def test_readout_sign_path_matches_readout_bwd(monkeypatch, mode):
     """The readout backward folded into dZ2's aggregation (the readout's H2 sign words and
@@ -680,13 +657,11 @@ def test_row_degree_model_trains_and_evaluates_consistently():
         FusedTrainStep(m, degree_on="col")
 
 
-@pytest.mark.parametrize("split", ["0", "1", "4"])
-def test_deferred_dw1_matches_one_call(split, monkeypatch):
+def test_deferred_dw1_matches_one_call():
     """defer_dw1 (the data-parallel overlap: everything but the conv1 weight gradients,
     then bgcn_train_step_dw1) writes the same bits as the one-call step, with the next
-    batch's preparation running beside both, under every dW1 form of the tail."""
+    batch's preparation running beside both."""
     from bigcn_amd import FusedTrainStep
-    monkeypatch.setenv("BGCN_DW1_SPLIT", split)
     b0, b1 = _synth(61, 32, 200), _synth(62, 32, 200)
     p = O.make_params(5000, 64, 64, 4, seed=41)
     res = []
@@ -709,16 +684,16 @@ def test_deferred_dw1_matches_one_call(split, monkeypatch):
         assert torch.equal(a, c), k
 
 
-@pytest.mark.parametrize("mode,classes,split", [("auto", 4, "0"), ("sparse", 2, "0"), ("dense", 4, "0"),
-                                                ("auto", 4, "1")])
-def test_optimizer_inside_step_matches_separate_launch(mode, classes, split, monkeypatch):
+# (ids as they have been since a third value chose the dW1 form; "0" was the sliced form, now the only one)
+@pytest.mark.parametrize("mode,classes", [("auto", 4), ("sparse", 2), ("dense", 4)],
+                         ids=["auto-4-0", "sparse-2-0", "dense-4-0"])
+def test_optimizer_inside_step_matches_separate_launch(mode, classes):
     """The single-process step with the Adam update inside its last launch
     (bgcn_step_args.adam) leaves bitwise the parameters, moments, weight images and losses
     of the step followed by its own bgcn_adam_step, over six steps with the next batch
     prepared beside each; an invalid step (bad label, step 3) is skipped and counted in
-    both.  dense / BGCN_DW1_SPLIT=1: the library falls back to the separate launch."""
+    both.  dense: the library falls back to the separate launch."""
     from bigcn_amd import FusedTrainStep
-    monkeypatch.setenv("BGCN_DW1_SPLIT", split)
     batches = [_synth(70 + k, 24, 150) for k in range(3)]
     for b in batches:
         b.y = b.y % classes

@@ -40,7 +40,7 @@ def main():
     from bigcn_amd import BiGCN, FusedTrainStep, _lib
     from bigcn_amd.optim import bigcn_adam
     L = ctypes.CDLL(_lib.LIB_PATH)
-    readers = [getattr(L, f"bgcn_bt_read_{tu}") for tu in ("sparse", "spmm", "bigcn")]
+    readers = [getattr(L, f"bgcn_bt_read_{tu}") for tu in ("sparse", "sparse_bwd", "spmm", "bigcn")]
     for r in readers:
         r.restype = ctypes.c_int
     dev = torch.device("cuda", 0)
