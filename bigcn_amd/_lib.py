@@ -40,6 +40,7 @@ BGCN_TREE_CENTRALITY_LDS = 2048   # longest tree bgcn_tree_centrality keeps in L
 BGCN_RANK_SIMILARITY_MAX = 32   # most rankings, and the largest k, of bgcn_rank_similarity
 BGCN_STATUS_TWO_PARENTS = 32
 BGCN_STATUS_CYCLE = 64
+BGCN_STATUS_BATCH_UNSORTED = 128   # bgcn_ebgcn_eval_step: the batch vector is not sorted (information)
 
 # every symbol include/bgcn.h declares (checked by tests/test_capi.py)
 EXPORTED_SYMBOLS = (
@@ -64,6 +65,7 @@ EXPORTED_SYMBOLS = (
     "bgcn_explain_sums_workspace_size", "bgcn_explain_sums", "bgcn_segment_rank_workspace_size", "bgcn_segment_rank",
     "bgcn_tree_centrality_workspace_size", "bgcn_tree_centrality", "bgcn_rank_similarity_workspace_size",
     "bgcn_rank_similarity", "bgcn_confusion",
+    "bgcn_ebgcn_eval_workspace_size", "bgcn_ebgcn_eval_step", "bgcn_ebgcn_eval_saved",
 )
 
 
@@ -138,6 +140,34 @@ class StepArgs(Structure):
         ("defer_dw1", c_int32),
         ("adam", c_void_p),
     ]
+
+
+class EbgcnDir(Structure):
+    """bgcn_ebgcn_dir (include/bgcn.h): one direction's parameters."""
+    _fields_ = [
+        ("conv1_w", c_void_p), ("conv1_b", c_void_p), ("conv2_w", c_void_p), ("conv2_b", c_void_p),
+        ("bn1_weight", c_void_p), ("bn1_bias", c_void_p), ("bn1_mean", c_void_p), ("bn1_var", c_void_p),
+        ("sim_conv_w", c_void_p),
+        ("sim_norm_weight", c_void_p), ("sim_norm_bias", c_void_p), ("sim_norm_mean", c_void_p),
+        ("sim_norm_var", c_void_p),
+        ("sim_out_w", c_void_p), ("sim_out_b", c_void_p), ("fc1_w", c_void_p),
+        ("bn1_eps", c_float), ("sim_norm_eps", c_float), ("infer", c_int32),
+    ]
+
+
+class EbgcnEvalArgs(Structure):
+    """bgcn_ebgcn_eval_args (include/bgcn.h)."""
+    _fields_ = [
+        ("batch", BatchDesc), ("td", EbgcnDir), ("bu", EbgcnDir), ("fc_w", c_void_p), ("fc_b", c_void_p),
+        ("in_feats", c_int64), ("num_classes", c_int64), ("edge_num", c_int32), ("degree_on", c_int32),
+        ("y", c_void_p), ("logp", c_void_p), ("loss", c_void_p), ("correct", c_void_p), ("pred", c_void_p),
+        ("td_edge_pred", c_void_p), ("bu_edge_pred", c_void_p), ("status", c_void_p),
+    ]
+
+
+class EbgcnEvalView(Structure):
+    """bgcn_ebgcn_eval_view (include/bgcn.h)."""
+    _fields_ = [("t_ptr", c_void_p), ("t_col", c_void_p), ("t_w", c_void_p), ("t_w2", c_void_p), ("slot", c_void_p)]
 
 
 _SIGS = {
@@ -232,6 +262,10 @@ _SIGS = {
     "bgcn_rank_similarity": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_confusion": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "bgcn_ebgcn_eval_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int]),
+    "bgcn_ebgcn_eval_step": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "bgcn_ebgcn_eval_saved": (c_int, [c_void_p, c_size_t, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int,
+                                      POINTER(EbgcnEvalView)]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

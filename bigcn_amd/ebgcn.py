@@ -19,6 +19,7 @@ reference's EBGCN forward applies none.
 """
 from __future__ import annotations
 
+import ctypes
 from collections import OrderedDict
 
 import torch
@@ -27,7 +28,8 @@ from . import _lib
 from ._lib import check, ptr, stream_handle
 from .bigcn import _num_graphs
 from .conv import GCNConv
-from .ops import _NO_TRAINING, build_graph, ebgcn_conv2_lin, edge_infer, gcn_conv, scatter_mean, spmm
+from .ops import (_NO_TRAINING, _check_ei, _i64c, build_graph, degree_code, ebgcn_conv2_lin, edge_infer, gcn_conv,
+                  scatter_mean, spmm)
 
 
 def _edge_network(hidden: int, name: str) -> torch.nn.Sequential:
@@ -157,3 +159,139 @@ class EBGCN(torch.nn.Module):
             check(_lib.lib().bgcn_head_forward(ptr(head), ptr(w), ptr(b), B, C, ptr(logp), stream_handle()))  # :228-229
             _raise_on(status)
         return logp, None, None
+
+    # ---- the evaluation loop (EBGCN.py:328-354) as one native call per batch
+    def _eval_tensors(self):
+        """The tensors ``bgcn_ebgcn_eval_args`` points at, in struct order (TD, BU, fc)."""
+        out = []
+        for d in (self.TDrumorGCN, self.BUrumorGCN):
+            sim = d.sim_network
+            out += [d.conv1.lin.weight, d.conv1.bias, d.conv2.lin.weight, d.conv2.bias,
+                    d.bn1.weight, d.bn1.bias, d.bn1.running_mean, d.bn1.running_var,
+                    sim.sim_valconv0.weight, sim.sim_valnorm0.weight, sim.sim_valnorm0.bias,
+                    sim.sim_valnorm0.running_mean, sim.sim_valnorm0.running_var,
+                    sim.sim_valconv_out.weight, sim.sim_valconv_out.bias, d.fc1.weight]
+        return out + [self.fc.weight, self.fc.bias]
+
+    def _eval_bind(self, dev):
+        """The pointer struct, refilled only when a parameter was rebound, moved or (a tensor the
+        kernels cannot read in place: not fp32 / contiguous / on ``dev``) changed."""
+        src = self._eval_tensors()
+        direct = [t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in src]
+        convs = (self.TDrumorGCN.conv1, self.TDrumorGCN.conv2, self.BUrumorGCN.conv1, self.BUrumorGCN.conv2)
+        settings = tuple(c.degree_on for c in convs) + (bool(self.args.edge_infer_td), bool(self.args.edge_infer_bu),
+                                                        self.TDrumorGCN.bn1.eps, self.BUrumorGCN.bn1.eps)
+        key = (dev, settings) + tuple((t.data_ptr(), t.dtype, None if ok else t._version)
+                                      for t, ok in zip(src, direct))
+        st = self.__dict__.get("_eval_state")
+        if st is not None and st["key"] == key:
+            return st
+        if len({c.degree_on for c in convs}) != 1:
+            raise ValueError("evaluate needs one degree_on for all four convolutions")
+        held = [t.detach() if ok else t.detach().to(device=dev, dtype=torch.float32).contiguous()
+                for t, ok in zip(src, direct)]
+        a = _lib.EbgcnEvalArgs()
+        names = [n for n, _ in _lib.EbgcnDir._fields_[:16]]
+        for k, (sub, d) in enumerate(((a.td, self.TDrumorGCN), (a.bu, self.BUrumorGCN))):
+            for j, n in enumerate(names):
+                setattr(sub, n, held[16 * k + j].data_ptr())
+            sub.bn1_eps, sub.sim_norm_eps = d.bn1.eps, d.sim_network.sim_valnorm0.eps
+            sub.infer = int(bool(getattr(self.args, d.infer_flag)))
+        a.fc_w, a.fc_b = held[32].data_ptr(), held[33].data_ptr()
+        a.in_feats, a.num_classes = int(self.args.input_features), int(self.args.num_class)
+        a.edge_num, a.degree_on = int(self.args.edge_num), degree_code(convs[0].degree_on)
+        if st is None or st["status"].device != dev:   # the workspace and the status words outlive a rebinding
+            st = {"status": torch.zeros(1, dtype=torch.int32, device=dev),
+                  "seen": torch.zeros(1, dtype=torch.int32, device=dev), "ws": None, "sizes": None}
+            self.__dict__["_eval_state"] = st
+        a.status = st["status"].data_ptr()
+        st.update(key=key, args=a, held=held)
+        return st
+
+    def evaluate(self, data, logp=None, pred=False):
+        """One batch of the reference's test loop (``EBGCN.py:328-354``: ``val_out, _, _ =
+        model(Batch_data); val_loss = F.nll_loss(val_out, y); _, val_pred = val_out.max(dim=1);
+        correct = val_pred.eq(y).sum()``) as one call (``bgcn_ebgcn_eval_step``), in eval mode
+        whatever ``model.training`` says and with no host sync.
+
+        Returns ``(loss, correct)`` (0-dim fp32 / int32 device tensors), plus ``pred`` ([B] int64)
+        when ``pred=True``.  ``logp``: an optional contiguous fp32 [B, C] output.  Sets
+        ``last_edge_pred``.  Validity of the batch's indices: :meth:`check_status`."""
+        x = data.x
+        dev = x.device
+        if not x.is_cuda:
+            raise _lib.BGCNError("bigcn_amd ops take device tensors (no CPU path)")
+        st = self._eval_bind(dev)
+        a = st["args"]
+        x = x if x.dtype == torch.float32 and x.stride(-1) == 1 and x.dim() == 2 else x.float().contiguous()
+        td_ei, bu_ei = _check_ei(data.edge_index), _check_ei(data.BU_edge_index)
+        batch, rootindex, y = _i64c(data.batch), _i64c(data.rootindex), _i64c(data.y)
+        N, F, B = int(x.size(0)), int(x.size(1)), _num_graphs(data)
+        Etd, Ebu = int(td_ei.size(1)), int(bu_ei.size(1))
+        C = int(a.num_classes)
+        if F != a.in_feats:
+            raise ValueError(f"data.x has {F} features, the model takes {a.in_feats}")
+        if rootindex.numel() != B or y.numel() != B or batch.numel() != N:
+            raise ValueError("batch must have one entry per node, rootindex and y one per tree")
+        if logp is not None and (logp.dtype != torch.float32 or not logp.is_contiguous() or logp.numel() != B * C
+                                 or logp.device != dev):
+            raise ValueError("logp must be a contiguous fp32 [B, C] tensor")
+        L = _lib.lib()
+        sizes = (N, B, F, Etd, Ebu)
+        if st["sizes"] != sizes:
+            need = L.bgcn_ebgcn_eval_workspace_size(N, B, F, Etd, Ebu, int(a.edge_num))
+            if st["ws"] is None or st["ws"].numel() < need or st["ws"].device != dev:
+                st["ws"] = _lib.workspace(need, dev)
+            st["sizes"] = sizes
+        ws = st["ws"]
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        correct = torch.empty(1, dtype=torch.int32, device=dev)
+        pr = torch.empty(B, dtype=torch.int64, device=dev) if pred else None
+        td_pred = torch.empty(Etd, dtype=torch.float32, device=dev) if a.td.infer else None
+        bu_pred = torch.empty(Ebu, dtype=torch.float32, device=dev) if a.bu.infer else None
+        b = a.batch
+        b.x, b.ldx, b.num_nodes, b.num_graphs = x.data_ptr(), x.stride(0), N, B
+        b.batch, b.rootindex = batch.data_ptr(), rootindex.data_ptr()
+        b.td_edge_index, b.td_num_edges, b.bu_edge_index, b.bu_num_edges = ptr(td_ei), Etd, ptr(bu_ei), Ebu
+        b.x_dtype = _lib.BGCN_DTYPE_F32
+        a.y, a.logp, a.loss, a.correct, a.pred = y.data_ptr(), ptr(logp), loss.data_ptr(), correct.data_ptr(), ptr(pr)
+        a.td_edge_pred, a.bu_edge_pred = ptr(td_pred), ptr(bu_pred)
+        check(L.bgcn_ebgcn_eval_step(ctypes.addressof(a), ptr(ws), ws.numel(), stream_handle()))
+        st["seen"].bitwise_or_(st["status"])   # the call zeroes its status word; check_status reads this one
+        self.last_edge_pred = (td_pred, bu_pred)
+        out = (loss.view(()), correct.view(()))
+        return out + (pr,) if pred else out
+
+    def validate(self, batches, metrics=None):
+        """The reference's test loop (``EBGCN.py:328-354``) without a host sync: every batch goes
+        through ``evaluate(batch, pred=True)`` and its loss, correct count, predictions and labels
+        into ``metrics.add(...)`` (:class:`bigcn_amd.metrics.EpochMetrics`; records are appended,
+        by default a new one sized for ``batches``).  Returns it; ``result()`` is the epoch's one
+        device-to-host read.  Validity of the batches themselves: :meth:`check_status`."""
+        from .metrics import EpochMetrics
+        batches = list(batches)
+        if metrics is None:
+            if not batches:
+                raise ValueError("validate needs at least one batch")
+            metrics = EpochMetrics(int(self.args.num_class), len(batches), batches[0].x.device)
+        elif len(metrics) + len(batches) > metrics.max_batches:
+            raise IndexError(f"metrics has room for {metrics.max_batches - len(metrics)} more batches, "
+                             f"{len(batches)} given")
+        for batch in batches:
+            loss, correct, pred = self.evaluate(batch, pred=True)
+            metrics.add(pred, batch.y, loss, correct)
+        return metrics
+
+    def check_status(self) -> None:
+        """One host sync: raise the ``IndexError`` ``forward`` raises when any batch evaluated since
+        the last check held an edge, root or tree index out of range (or a label outside
+        ``[0, num_class)``)."""
+        st = self.__dict__.get("_eval_state")
+        if st is None:
+            return
+        s = int(st["seen"].item())
+        st["seen"].zero_()
+        if s & 1:
+            raise IndexError("the batch holds an edge, root or tree index out of range")
+        if s & 2:
+            raise IndexError("the batch holds a label outside [0, num_class)")

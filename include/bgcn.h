@@ -688,6 +688,87 @@ int bgcn_train_step_saved(void* workspace, size_t workspace_bytes, int64_t num_n
 int bgcn_join_side(bgcn_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * EBGCN evaluation step: the test loop body of model/Twitter/EBGCN.py:328-354
+ *   model.eval(); val_out, _, _ = model(Batch_data); val_loss = F.nll_loss(val_out, Batch_data.y)
+ *   _, val_pred = val_out.max(dim=1); correct = val_pred.eq(Batch_data.y).sum()
+ * as one call: one launch sequence, no host round trip, no allocation (everything lives in the
+ * caller's workspace).  Additive entry points: BGCN_ABI_VERSION is unchanged.
+ *
+ * Both directions' adjacency structure is built once (the unweighted pair build); conv1 of both
+ * directions shares one pass over x; bgcn_edge_infer and bgcn_ebgcn_conv2_lin run per direction;
+ * conv2 aggregates over the same t_ptr / t_col with a second value array that a reweight step
+ * fills from edge_pred: the weighted degree (each node's self loop of weight 1 added last, input
+ * self loops dropped, summed on the side degree_on names, in row order), dinv = deg^-1/2
+ * (inf -> 0) and dinv[src] * edge_pred * dinv[dst].  For an edge list without self loops (every
+ * propagation tree) these are bgcn_build_graph(edge_weight = edge_pred)'s values; that build
+ * gives a node with an input self loop the loop's weight instead of 1.  A direction with
+ * infer == 0 or no edges aggregates conv2 with conv1's values.  The eval-mode BatchNorms (bn1 and
+ * sim_valnorm0 of both directions) are folded inside the call.  The readout runs one workgroup
+ * per tree: the mean of relu(h2) over the tree's nodes summed in node order, h1[root] copied
+ * (zeros for a tree without nodes, as scatter_mean), the head row laid out BU first
+ * (EBGCN.py:227), then fc, log_softmax, the tree's NLL term and its argmax (the first maximal
+ * class, as torch's max); a last single-workgroup launch reduces the mean loss and the correct
+ * count over the trees in a fixed order.  Deterministic (no float atomics).
+ * A batch vector that is not sorted sets BGCN_STATUS_BATCH_UNSORTED (information, the results
+ * are valid): each tree's workgroup then picks its nodes out of the whole vector, in node order.
+ * An edge, root or tree index out of range contributes zeros and sets bit 0 of *status; a label
+ * outside [0, C) contributes no loss and sets bit 1.  *status is zeroed by the call.
+ *
+ * BGCN_EINVAL with the first failing check's message, before any HIP call: "bad sizes",
+ * "num_classes must be in [1, 16]", "edge_num must be in [1, 8]", a nonzero droprate ("drops no
+ * edges"), x that is not dense fp32, in_feats / ldx not multiples of 4, "null parameter pointer",
+ * a null loss / correct / status, "workspace too small".
+ * -------------------------------------------------------------------------- */
+#define BGCN_STATUS_BATCH_UNSORTED 128
+typedef struct bgcn_ebgcn_dir {   /* one direction's parameters (TDrumorGCN / BUrumorGCN), fp32 */
+  const float* conv1_w; const float* conv1_b;   /* conv1.lin.weight [64, F], conv1.bias [64]   */
+  const float* conv2_w; const float* conv2_b;   /* conv2.lin.weight [64, 64 + F], conv2.bias   */
+  const float* bn1_weight; const float* bn1_bias;              /* bn1, [64 + F] each            */
+  const float* bn1_mean; const float* bn1_var;
+  const float* sim_conv_w;                      /* sim_network.sim_valconv0.weight [64, 64]    */
+  const float* sim_norm_weight; const float* sim_norm_bias;    /* sim_valnorm0, [64] each       */
+  const float* sim_norm_mean; const float* sim_norm_var;
+  const float* sim_out_w; const float* sim_out_b;              /* sim_valconv_out [64], [1]     */
+  const float* fc1_w;                           /* fc1.weight [edge_num, 64]                   */
+  float bn1_eps; float sim_norm_eps;
+  int32_t infer;                                /* edge_infer_td / edge_infer_bu               */
+} bgcn_ebgcn_dir;
+typedef struct bgcn_ebgcn_eval_args {
+  bgcn_batch batch;              /* dense fp32 x; no DropEdge                */
+  bgcn_ebgcn_dir td, bu;
+  const float* fc_w;             /* [C, 256]                                 */
+  const float* fc_b;             /* [C]                                      */
+  int64_t in_feats;              /* F, a multiple of 4                       */
+  int64_t num_classes;           /* C in [1, 16]                             */
+  int32_t edge_num;              /* in [1, 8]                                */
+  int32_t degree_on;             /* BGCN_DEGREE_ON_COL / _ROW                */
+  const int64_t* y;              /* [B] labels, or NULL (loss 0, correct 0)  */
+  float* logp;                   /* [B, C] or NULL                           */
+  float* loss;                   /* [1] mean NLL                             */
+  int32_t* correct;              /* [1]                                      */
+  int64_t* pred;                 /* [B] or NULL                              */
+  float* td_edge_pred;           /* [E_td] or NULL                           */
+  float* bu_edge_pred;           /* [E_bu] or NULL                           */
+  int32_t* status;               /* [1]                                      */
+} bgcn_ebgcn_eval_args;
+size_t bgcn_ebgcn_eval_workspace_size(int64_t num_nodes, int64_t num_graphs, int64_t in_feats,
+                                      int64_t td_num_edges, int64_t bu_num_edges, int edge_num);
+int bgcn_ebgcn_eval_step(const bgcn_ebgcn_eval_args* args, void* workspace, size_t workspace_bytes,
+                         bgcn_stream_t stream);
+/* The pieces of the last bgcn_ebgcn_eval_step run in `workspace` with these sizes (valid until it
+ * is reused), for inspection: dir 0 = TD, 1 = BU.  t_ptr [N + 1] / t_col [E + N] = the by-target
+ * structure; t_w = conv1's values; t_w2 = the reweighted values conv2 aggregated with (written
+ * only for a direction with infer != 0 and edges); slot [E] = each edge's entry in that structure
+ * (-1: a dropped self loop or an edge with an end out of range). */
+typedef struct bgcn_ebgcn_eval_view {
+  const int32_t* t_ptr; const int32_t* t_col; const float* t_w; const float* t_w2;
+  const int32_t* slot;
+} bgcn_ebgcn_eval_view;
+int bgcn_ebgcn_eval_saved(void* workspace, size_t workspace_bytes, int64_t num_nodes, int64_t num_graphs,
+                          int64_t in_feats, int64_t td_num_edges, int64_t bu_num_edges, int edge_num,
+                          int dir, bgcn_ebgcn_eval_view* out);
+
+/* --------------------------------------------------------------------------
  * Optimiser step of the training loop: torch.optim.Adam with the reference's three
  * parameter groups (BiGCN_Twitter.py:146-153, step at :189) as ONE fused launch.
  * amsgrad = False; weight_decay is L2 added to the gradient (torch Adam semantics).
