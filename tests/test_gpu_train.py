@@ -684,23 +684,13 @@ def test_deferred_dw1_matches_one_call():
         assert torch.equal(a, c), k
 
 
-# (ids as they have been since a third value chose the dW1 form; "0" was the sliced form, now the only one)
-@pytest.mark.parametrize("mode,classes", [("auto", 4), ("sparse", 2), ("dense", 4)],
-                         ids=["auto-4-0", "sparse-2-0", "dense-4-0"])
-def test_optimizer_inside_step_matches_separate_launch(mode, classes):
-    """The single-process step with the Adam update inside its last launch
-    (bgcn_step_args.adam) leaves bitwise the parameters, moments, weight images and losses
-    of the step followed by its own bgcn_adam_step, over six steps with the next batch
-    prepared beside each; an invalid step (bad label, step 3) is skipped and counted in
-    both.  dense: the library falls back to the separate launch."""
+def check_optimizer_inside_step(mode, classes, batches, bad, F=5000):
+    """Six steps (three batches, the invalid batch `bad` as step 3, the next batch prepared beside
+    each) with fuse_optimizer on and off: losses, parameters, moments, the image buffer, the skip
+    count and the step count are bitwise the same.  Also run at small shapes by
+    tests/test_gpu_adam.py."""
     from bigcn_amd import FusedTrainStep
-    batches = [_synth(70 + k, 24, 150) for k in range(3)]
-    for b in batches:
-        b.y = b.y % classes
-    bad = _synth(73, 24, 150)
-    bad.y = bad.y.clone() % classes
-    bad.y[2] = 9
-    p = O.make_params(5000, 64, 64, classes, seed=43)
+    p = O.make_params(F, 64, 64, classes, seed=43)
     runs = []
     for fuse in (True, False):
         m = _model(p, mode, classes)
@@ -726,3 +716,20 @@ def test_optimizer_inside_step_matches_separate_launch(mode, classes):
     assert a[4] == b[4] == 1
     assert a[5] == b[5] == 6
 
+
+# (ids as they have been since a third value chose the dW1 form; "0" was the sliced form, now the only one)
+@pytest.mark.parametrize("mode,classes", [("auto", 4), ("sparse", 2), ("dense", 4)],
+                         ids=["auto-4-0", "sparse-2-0", "dense-4-0"])
+def test_optimizer_inside_step_matches_separate_launch(mode, classes):
+    """The single-process step with the Adam update inside its last launch
+    (bgcn_step_args.adam) leaves bitwise the parameters, moments, weight images and losses
+    of the step followed by its own bgcn_adam_step, over six steps with the next batch
+    prepared beside each; an invalid step (bad label, step 3) is skipped and counted in
+    both.  dense: the library falls back to the separate launch."""
+    batches = [_synth(70 + k, 24, 150) for k in range(3)]
+    for b in batches:
+        b.y = b.y % classes
+    bad = _synth(73, 24, 150)
+    bad.y = bad.y.clone() % classes
+    bad.y[2] = 9
+    check_optimizer_inside_step(mode, classes, batches, bad)
