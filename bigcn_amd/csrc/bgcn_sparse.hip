@@ -288,13 +288,27 @@ __global__ __launch_bounds__(256) void k_conv1_rows2(SparseState S, float* __res
 // t: slots 2(8t + j) + h), so each lane hashes only its own keep words and the steps past
 // the root's non-zeros are skipped; the keep bits are exact in bf16 (three products).
 //
-// Every wave works on ONE 32-node tile: a block takes half a work item (tiles 4 half ..
-// 4 half + 3; the second half of an item of <= 128 nodes exits at once), so no wave runs two
-// tiles in series, and each lane loads its H1 A-fragment (row r32, columns [32h, 32h + 32)
-// of direction d: eight 16-byte loads, a 128-byte run) straight into registers at the
-// kernel's start, under the B fill - no LDS staging of H1 (the block's LDS is the B operand
-// only).  Tried a block per whole item (two tiles per wave in series, H1 staged through
-// LDS): the kernel was the fill plus two tiles' products on the items of 256 nodes.
+// Every wave works on ONE 32-node tile and a block is one (work item, direction): 512
+// threads, wave w takes tile w of the item's <= 8 (kChunk = 256 nodes), so no wave runs two
+// tiles in series and the B operand - the 24.6 KB split W2 image, the root's 32 slots and
+// their W2^T rows, a dependent chain item -> root -> cols -> W2^T - is filled once per item
+// and direction, by all 512 threads.  (The half-item form before it, 256-thread blocks of
+// four tiles, filled twice for every item over 128 nodes; beside the next batch's pass over
+// X those loads are what queues.)  A wave whose tile lies past the item's end computes
+// nothing and stays for the spill rounds' barriers.  Each lane loads its H1 A-fragment (row
+// r32, columns [32h, 32h + 32) of direction d: eight 16-byte loads, a 128-byte run) straight
+// into registers - no LDS staging of H1 (the block's LDS is the B operand only) - and
+// requests it after the fill's loads (all twelve 16-byte loads are in flight before the
+// fill's barrier).  With 32-bit node indices the wave takes 96 registers, no scratch
+// (__launch_bounds__(512, 5)).  What that does NOT buy: a block is two waves per SIMD, 192
+// registers, so beside the next batch's pass over X (201 registers a wave) it fits on a CU
+// that holds one block of the pass (304 free: one block, as two of the 120-register
+// half-item blocks did) and not on one that holds two (96 free).  In the step its blocks
+// still start over ~65 us in three rounds of ~20 us (profiles/r07_conv2_blocks.txt); the
+// launch is 80 us there either way, 20.5 -> 17.7 us alone.  Fitting beside two blocks of
+// the pass needs one wave per SIMD at <= 96 registers (a four-wave block) or 48 a wave.
+// Tried a block per whole item with two tiles per wave in series (H1 staged through LDS):
+// the kernel was the fill plus two tiles' products on the items of 256 nodes.
 // Tried per-tree root images built by extra blocks of conv1's launch (one dependent level
 // less in this fill): conv1 alone 15.6 -> 19.5 us for its 2B extra blocks, conv2 unchanged
 // (20.6 -> 20.2), the step not faster (profiles/r05_pass_regs_ab.txt and the round-5
@@ -302,69 +316,73 @@ __global__ __launch_bounds__(256) void k_conv1_rows2(SparseState S, float* __res
 constexpr int kC2K = H + kCap;           // B rows: 64 H1 columns + 32 root slot positions
 constexpr int kC2Ld16 = kC2K + 8;        // bf16 row stride of the split B (16-byte aligned)
 static_assert(kC2Ld16 == kW2sLd, "conv2's B rows are the prologue image's rows");
-#ifndef BGCN_C2H_WAVES
-#define BGCN_C2H_WAVES 1   // min waves per SIMD (register budget: 5 -> <= 96, beside two waves of the pass)
-#endif
-__global__ __launch_bounds__(256, BGCN_C2H_WAVES) void k_conv2_half(SparseState S, const float* __restrict__ H1,
-                                                    float* __restrict__ Z2, KeepSrc keep) {
+constexpr int kC2Threads = 512;          // 8 waves: one per 32-node tile of an item
+static_assert(kChunk == 32 * (kC2Threads / 64), "a wave per tile of a work item");
+__global__ __launch_bounds__(kC2Threads, 5) void k_conv2_item(SparseState S, const float* __restrict__ H1,
+                                                              float* __restrict__ Z2, KeepSrc keep) {
   BT_BEGIN
   if (!use_sparse(S)) return;
-  const int item = int(blockIdx.x >> 1), half = int(blockIdx.x & 1);
+  const int item = int(blockIdx.x);
   if (item >= S.tree_item0[S.B]) return;
   __shared__ __attribute__((aligned(16))) __bf16 Bs[3][H * kC2Ld16];   // hi, mid, lo
   __shared__ uint32_t rk[kCap];
   const int d = blockIdx.y;
-  const int64_t beg = S.item_beg[item], end = S.item_end[item];
-  if (beg + 128 * half >= end) return;               // block-uniform: no tile in this half
+  const int32_t beg = S.item_beg[item], end = S.item_end[item];   // node indices: 32-bit, as stored
   const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, r32 = l & 31, h = l >> 5;
-  const int t = 4 * half + wv;
-  const int64_t i0 = beg + 32 * t;
-  const int64_t i = i0 + r32;
+  const int32_t i0 = beg + 32 * wv;
+  const int32_t i = i0 + r32;
   const bool ok = i < end;
   const bool live = i0 < end;                        // wave-uniform: the wave has a tile
-  // this lane's A-fragment rows (clamped: a row past the item reads the item's last row and
-  // is masked by `ok`), requested before the fill.  (Requested after it, the 32 registers
-  // stay free during the fill, 114 -> ~84 per wave - tried, not kept.)
-  float4 hv[8];
-  const float* hsrc = H1 + min<int64_t>(i, end - 1) * (2 * H) + d * H + 32 * h;
-#pragma unroll
-  for (int u = 0; u < 8; ++u) hv[u] = ld4(hsrc + 4 * u);
   const int64_t r = S.item_root[item];
   const float sc = keep.scale();
   const int64_t K2 = S.F + H;
   const float* w2t = S.w2t + int64_t(d) * K2 * H;
-  {
-    const __bf16* src = S.w2s + int64_t(d) * 3 * H * kW2sLd;
-    for (int e = threadIdx.x; e < 3 * H * 8; e += 256) {
-      const int part = e / (H * 8), o = (e / 8) % H, q = (e % 8) * 8;
-      *reinterpret_cast<uint4*>(&Bs[part][o * kC2Ld16 + q]) =
-          *reinterpret_cast<const uint4*>(src + (int64_t(part) * H + o) * kW2sLd + q);
-    }
+  // the fill, once per block: every thread takes three 16-byte pieces of the split W2 image
+  // and four outputs of one root slot (unconditional loads from a clamped slot / column,
+  // selects after; zero past rn).  All of its loads are requested before the H1 fragment.
+  static_assert(3 * H * 8 == 3 * kC2Threads && kCap * (H / 4) == kC2Threads, "one fill round per thread");
+  const __bf16* src = S.w2s + int64_t(d) * 3 * H * kW2sLd;
+  uint4 im[3];
+#pragma unroll
+  for (int u = 0; u < 3; ++u) {
+    const int e = int(threadIdx.x) + u * kC2Threads;
+    const int part = e / (H * 8), o = (e / 8) % H, q = (e % 8) * 8;
+    im[u] = *reinterpret_cast<const uint4*>(src + (int64_t(part) * H + o) * kW2sLd + q);
   }
   const int rn_all = S.nnz[r];
   const int rn = min(rn_all, kCap);   // root slots in the ELL (the rest spilled)
-  // the root slots, with unconditional loads (clamped slot / column), selects after
-  if (threadIdx.x < kCap)
-    rk[threadIdx.x] = threadIdx.x < rn ? uint32_t(H + S.cols[r * kCap + threadIdx.x]) : 0u;
-  for (int e = threadIdx.x; e < kCap * (H / 4); e += 256) {   // (zero past rn)
-    const int s = e >> 4, q = (e & 15) * 4;
-    const int64_t slot = r * kCap + s;
-    const int32_t col = min(max(S.cols[slot], 0), int32_t(S.F - 1));
-    const float val = S.vals[slot];
-    const float4 w = ld4(w2t + int64_t(H + col) * H + q);
-    const float av = s < rn ? sc * fmaxf(val, 0.f) : 0.f;
-    const float vv[4] = {av * w.x, av * w.y, av * w.z, av * w.w};
-    const int k = H + (s & 1) * (kCap / 2) + (s >> 1);
+  const int fs = int(threadIdx.x) >> 4, fq = (int(threadIdx.x) & 15) * 4;
+  const int64_t slot = r * kCap + fs;
+  const int32_t fcol_raw = S.cols[slot];
+  const float fval = S.vals[slot];
+  const float4 fw = ld4(w2t + int64_t(H + min(max(fcol_raw, 0), int32_t(S.F - 1))) * H + fq);
+  // this lane's A-fragment rows (clamped: a row past the item reads the item's last row and
+  // is masked by `ok`)
+  float4 hv[8];
+  const float* hsrc = H1 + int64_t(min(i, end - 1)) * (2 * H) + d * H + 32 * h;
+#pragma unroll
+  for (int u = 0; u < 8; ++u) hv[u] = ld4(hsrc + 4 * u);
+#pragma unroll
+  for (int u = 0; u < 3; ++u) {
+    const int e = int(threadIdx.x) + u * kC2Threads;
+    const int part = e / (H * 8), o = (e / 8) % H, q = (e % 8) * 8;
+    *reinterpret_cast<uint4*>(&Bs[part][o * kC2Ld16 + q]) = im[u];
+  }
+  if ((threadIdx.x & 15) == 0) rk[fs] = fs < rn ? uint32_t(H + fcol_raw) : 0u;
+  {
+    const float av = fs < rn ? sc * fmaxf(fval, 0.f) : 0.f;
+    const float vv[4] = {av * fw.x, av * fw.y, av * fw.z, av * fw.w};
+    const int k = H + (fs & 1) * (kCap / 2) + (fs >> 1);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const int o = (q + u) * kC2Ld16 + k;
+      const int o = (fq + u) * kC2Ld16 + k;
       split3_bf16(vv[u], Bs[0][o], Bs[1][o], Bs[2][o]);
     }
   }
   __syncthreads();
   BT_MARK(2, 0);
-  // a wave without a tile (the half's last tiles past a short item) computes nothing but
-  // stays for the spill rounds' barriers
+  // a wave without a tile (past a short item's end) computes nothing but stays for the
+  // spill rounds' barriers
   const uint32_t ni = uint32_t(ok ? i : beg);
   const uint32_t kb = keep.base(ni);
   f32x16 acc0 = {}, acc1 = {};
@@ -398,7 +416,7 @@ __global__ __launch_bounds__(256, BGCN_C2H_WAVES) void k_conv2_half(SparseState 
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  if (t == 4 * half) BT_MARK(2, 2);
+  if (wv == 0) BT_MARK(2, 2);
   // the root slots (exact 0/1 keep bits times the staged root rows, three products); a root
   // row over the ELL cap continues from the spill pool in rounds of kCap entries
   const int64_t off = rn_all > kCap ? S.ovf_off[r] : 0;
@@ -410,7 +428,7 @@ __global__ __launch_bounds__(256, BGCN_C2H_WAVES) void k_conv2_half(SparseState 
       const int tk = min(int(threadIdx.x), kCap - 1);
       const uint2 ek = S.ovf[off + min(c0 + tk, nsp - 1)];
       if (threadIdx.x < kCap) rk[threadIdx.x] = uint32_t(H + min(max(int32_t(ek.x), 0), int32_t(S.F - 1)));
-      for (int e = threadIdx.x; e < kCap * (H / 4); e += 256) {
+      for (int e = threadIdx.x; e < kCap * (H / 4); e += kC2Threads) {
         const int s = e >> 4, q = (e & 15) * 4;
         const uint2 ent = S.ovf[off + min(c0 + s, nsp - 1)];
         const float4 w = ld4(w2t + int64_t(H + min(max(int32_t(ent.x), 0), int32_t(S.F - 1))) * H + q);
@@ -460,10 +478,10 @@ __global__ __launch_bounds__(256, BGCN_C2H_WAVES) void k_conv2_half(SparseState 
   }
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
-    const int64_t ii = i0 + (q & 3) + 8 * (q >> 2) + 4 * h;
+    const int32_t ii = i0 + (q & 3) + 8 * (q >> 2) + 4 * h;
     if (ii < end) {
-      Z2[ii * (2 * H) + d * H + r32] = acc0[q];
-      Z2[ii * (2 * H) + d * H + 32 + r32] = acc1[q];
+      Z2[int64_t(ii) * (2 * H) + d * H + r32] = acc0[q];
+      Z2[int64_t(ii) * (2 * H) + d * H + 32 + r32] = acc1[q];
     }
   }
   BT_END(2);
@@ -576,7 +594,7 @@ int sparse_items(SparseState& S, const int32_t* tree_ptr, const int64_t* rootind
 }
 
 int sparse_conv2(SparseState& S, const float* H1, float* Z2, KeepSrc keep, hipStream_t s) {
-  hipLaunchKernelGGL(k_conv2_half, dim3(unsigned(2 * S.max_items), 2), dim3(256), 0, s, S, H1, Z2, keep);
+  hipLaunchKernelGGL(k_conv2_item, dim3(unsigned(S.max_items), 2), dim3(kC2Threads), 0, s, S, H1, Z2, keep);
   BGCN_CHECK_LAUNCH();
   return BGCN_OK;
 }
