@@ -5,8 +5,10 @@ Drop-in symbols for the reference's hot path (cwkd/BiGCN):
 * ``GCNConv``       <- ``from torch_geometric.nn import GCNConv``   (BiGCN_Twitter.py:15)
 * ``scatter_mean``  <- ``from torch_scatter import scatter_mean``   (BiGCN_Twitter.py:6)
 * ``TDrumorGCN``, ``BUrumorGCN``, ``BiGCN`` (Twitter, 4 classes), ``Net`` (Weibo, 2 classes)
-* ``EBGCN`` - the edge-enhanced model (model/Twitter/EBGCN.py) for inference: eval forward on
-  the edge-inference kernel (``edge_infer``), reference checkpoints load strictly
+* ``EBGCN`` - the edge-enhanced model (model/Twitter/EBGCN.py): eval forward on the edge-inference
+  kernel (``edge_infer``), reference checkpoints load strictly; ``EBGCN.train_forward`` is the
+  reference's training forward with autograd, on ``edge_infer_train`` (the five per-edge networks
+  with batch-statistics BatchNorm, the Bayesian branch, the KL edge loss and their backward)
 * ``explain`` / ``segment_rank`` - the reference's analysis (explain_PHEME.py): per-stage node sums and
   per-tree rankings of a whole batch, for ``BiGCN`` / ``Net`` / ``EBGCN`` in eval mode
 * ``compare`` / ``tree_centrality`` / ``rank_similarity`` - the reference's comparison
@@ -28,13 +30,13 @@ from .ebgcn import EBGCN
 from .explain import explain, segment_rank
 from . import metrics
 from .metrics import EpochMetrics, class_metrics, confusion, evaluation4class, evaluationclass
-from .ops import Graph, bigcn_encoder, build_graph, edge_infer, gcn_conv, scatter_mean, spmm
+from .ops import Graph, bigcn_encoder, build_graph, edge_infer, edge_infer_train, gcn_conv, scatter_mean, spmm
 from .optim import FusedAdam, bigcn_adam
 from .train import FusedTrainStep
 
 __all__ = ["GCNConv", "scatter_mean", "TDrumorGCN", "BUrumorGCN", "BiGCN", "Net", "make_optimizer",
            "Graph", "build_graph", "gcn_conv", "spmm", "bigcn_encoder", "FusedAdam", "bigcn_adam",
-           "FusedTrainStep", "EBGCN", "edge_infer", "explain", "segment_rank",
+           "FusedTrainStep", "EBGCN", "edge_infer", "edge_infer_train", "explain", "segment_rank",
            "compare", "tree_centrality", "rank_similarity",
            "metrics", "confusion", "class_metrics", "evaluation4class", "evaluationclass", "EpochMetrics"]
 __version__ = "0.1.0"

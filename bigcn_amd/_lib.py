@@ -66,6 +66,7 @@ EXPORTED_SYMBOLS = (
     "bgcn_tree_centrality_workspace_size", "bgcn_tree_centrality", "bgcn_rank_similarity_workspace_size",
     "bgcn_rank_similarity", "bgcn_confusion",
     "bgcn_ebgcn_eval_workspace_size", "bgcn_ebgcn_eval_step", "bgcn_ebgcn_eval_saved",
+    "bgcn_edge_infer_train_workspace_size", "bgcn_edge_infer_train_fwd", "bgcn_edge_infer_train_bwd",
 )
 
 
@@ -170,6 +171,38 @@ class EbgcnEvalView(Structure):
     _fields_ = [("t_ptr", c_void_p), ("t_col", c_void_p), ("t_w", c_void_p), ("t_w2", c_void_p), ("slot", c_void_p)]
 
 
+class EdgeNet(Structure):
+    """bgcn_edge_net (include/bgcn.h): one per-edge network."""
+    _fields_ = [("conv_w", c_void_p), ("norm_weight", c_void_p), ("norm_bias", c_void_p), ("out_w", c_void_p),
+                ("out_b", c_void_p), ("eps", c_float)]
+
+
+class EdgeTrainFwdArgs(Structure):
+    """bgcn_edge_train_fwd_args (include/bgcn.h)."""
+    _fields_ = [
+        ("h", c_void_p), ("ldh", c_int64), ("num_nodes", c_int64), ("hid", c_int64),
+        ("edge_index", c_void_p), ("num_edges", c_int64), ("net", EdgeNet * 5),
+        ("fc1_w", c_void_p), ("fc2_w", c_void_p), ("edge_num", c_int32), ("noise", c_void_p),
+        ("edge_pred", c_void_p), ("edge_loss", c_void_p), ("s", c_void_p), ("p", c_void_p), ("p_y", c_void_p),
+        ("sim_mean", c_void_p), ("sim_rstd", c_void_p), ("num_valid", c_void_p),
+        ("batch_mean", c_void_p), ("batch_var", c_void_p), ("status", c_void_p),
+    ]
+
+
+class EdgeTrainBwdArgs(Structure):
+    """bgcn_edge_train_bwd_args (include/bgcn.h)."""
+    _fields_ = [
+        ("h", c_void_p), ("ldh", c_int64), ("num_nodes", c_int64), ("hid", c_int64),
+        ("edge_index", c_void_p), ("num_edges", c_int64), ("sim", EdgeNet),
+        ("fc1_w", c_void_p), ("edge_num", c_int32),
+        ("s", c_void_p), ("p", c_void_p), ("p_y", c_void_p), ("sim_mean", c_void_p), ("sim_rstd", c_void_p),
+        ("num_valid", c_void_p), ("d_pred", c_void_p), ("d_loss", c_void_p),
+        ("d_h", c_void_p), ("ldd", c_int64),
+        ("d_conv_w", c_void_p), ("d_norm_weight", c_void_p), ("d_norm_bias", c_void_p),
+        ("d_out_w", c_void_p), ("d_out_b", c_void_p), ("d_fc1_w", c_void_p),
+    ]
+
+
 _SIGS = {
     "bgcn_abi_version": (c_int, []),
     "bgcn_last_error": (c_char_p, []),
@@ -266,6 +299,9 @@ _SIGS = {
     "bgcn_ebgcn_eval_step": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_ebgcn_eval_saved": (c_int, [c_void_p, c_size_t, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int,
                                       POINTER(EbgcnEvalView)]),
+    "bgcn_edge_infer_train_workspace_size": (c_size_t, [c_int64, c_int64]),
+    "bgcn_edge_infer_train_fwd": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "bgcn_edge_infer_train_bwd": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

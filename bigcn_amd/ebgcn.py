@@ -1,4 +1,4 @@
-"""EBGCN for inference: the reference's module structure and state_dict on the HIP path.
+"""EBGCN: the reference's module structure and state_dict on the HIP path.
 
 Mirrors ``model/Twitter/EBGCN.py:23-230`` (``TDrumorGCN``, ``BUrumorGCN``, ``EBGCN``).  Module
 and parameter names and shapes are the reference's - the five per-direction networks
@@ -6,10 +6,12 @@ and parameter names and shapes are the reference's - the five per-direction netw
 ``fc2``, ``bn1`` and every ``num_batches_tracked`` included - so a checkpoint's
 ``model_state_dict`` loads with ``load_state_dict(..., strict=True)``.
 
-This is the inference-only path: ``model.eval()(data)`` returns ``(log_probs, None, None)``.
+Inference: ``model.eval()(data)`` returns ``(log_probs, None, None)``.
 The reference's evaluation loop (``EBGCN.py:338``) discards both edge losses, which depend on a
 ``th.normal`` draw; the Bayesian networks are therefore carried (for the checkpoint) but never
-run.  In training mode ``forward`` raises ``NotImplementedError``.
+run.  In training mode ``forward`` raises ``NotImplementedError``; the training forward is
+:meth:`EBGCN.train_forward` (autograd throughout, the edge inference of both directions on
+:func:`bigcn_amd.ops.edge_infer_train`).
 
 Per direction (``EBGCN.py:61-93``): conv1 -> :func:`bigcn_amd.ops.edge_infer` (the
 edge-inference kernel) -> conv2's lin over ``relu(bn1(cat(h1, x[root])))``
@@ -28,8 +30,8 @@ from . import _lib
 from ._lib import check, ptr, stream_handle
 from .bigcn import _num_graphs
 from .conv import GCNConv
-from .ops import (_NO_TRAINING, _check_ei, _i64c, build_graph, degree_code, ebgcn_conv2_lin, edge_infer, gcn_conv,
-                  scatter_mean, spmm)
+from .ops import (_NO_TRAINING, _check_ei, _i64c, build_graph, degree_code, ebgcn_conv2_lin, edge_infer,
+                  edge_infer_train, gcn_conv, scatter_mean, spmm)
 
 
 def _edge_network(hidden: int, name: str) -> torch.nn.Sequential:
@@ -74,10 +76,42 @@ class _EdgeRumorGCN(torch.nn.Module):
         self.dropout = torch.nn.Dropout(getattr(args, "dropout", 0.5))   # held, never applied (:57)
         self.bn1 = torch.nn.BatchNorm1d(H + F)
 
-    def edge_infer(self, x, edge_index, status=None):
-        """``(None, edge_pred [E])``: the reference returns ``(edge_loss, edge_pred)``
-        (``:95-116``); the loss needs the Bayesian draw and is not computed here."""
+    def edge_infer(self, x, edge_index, status=None, noise=None, generator=None):
+        """``(edge_loss, edge_pred [E])`` (``:95-116``).  In training mode both come from
+        :func:`bigcn_amd.ops.edge_infer_train` and carry gradients; in eval mode the loss, which
+        needs the Bayesian draw and which the evaluation loop drops, is ``None``."""
+        if self.training:
+            return edge_infer_train(x, edge_index, self, noise=noise, generator=generator, status=status)
         return None, edge_infer(x, edge_index, self, status=status)
+
+    def _train_encode(self, data, noise, generator, status):
+        """The training forward of one direction (``:61-93``) with autograd: ``(x [B, 128],
+        edge_loss or None)``.  The ``[N, 64 + F]`` concat is kept dense."""
+        x = data.x.float()
+        ei = getattr(data, self.edge_key)
+        batch, rootindex = data.batch, data.rootindex
+        N = x.size(0)
+        h1 = gcn_conv(x, ei, self.conv1.lin.weight, self.conv1.bias, degree_on=self.conv1.degree_on)   # :64
+        edge_loss = edge_pred = None
+        if bool(getattr(self.args, self.infer_flag)):                          # :67-70
+            edge_loss, edge_pred = edge_infer_train(h1, ei, self, noise=noise, generator=generator, status=status)
+        root_of_node = rootindex[batch]
+        cat = torch.cat((h1, x.index_select(0, root_of_node)), 1)              # :72-78
+        if N != 1:                                                             # :80-81, batch statistics
+            bn = self.bn1
+            factor = 0.0
+            if bn.track_running_stats and bn.num_batches_tracked is not None:
+                bn.num_batches_tracked += 1
+                factor = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else bn.momentum
+            cat = torch.nn.functional.batch_norm(cat, bn.running_mean, bn.running_var, bn.weight, bn.bias, True,
+                                                 factor, bn.eps)
+        cat = torch.relu(cat)                                                  # :82
+        h2 = gcn_conv(cat, ei, self.conv2.lin.weight, self.conv2.bias, edge_weight=edge_pred,
+                      degree_on=self.conv2.degree_on)                          # :84
+        # :65 x2 = copy.copy(x) is a copy outside the autograd graph: as in the reference, no
+        # gradient reaches conv1 through the root rows of the readout (:86-90)
+        h = torch.cat((torch.relu(h2), h1.detach().index_select(0, root_of_node)), 1)
+        return scatter_mean(h, batch, dim=0, dim_size=_num_graphs(data)), edge_loss   # :92
 
     def _encode(self, data, status):
         x = data.x.float()
@@ -159,6 +193,28 @@ class EBGCN(torch.nn.Module):
             check(_lib.lib().bgcn_head_forward(ptr(head), ptr(w), ptr(b), B, C, ptr(logp), stream_handle()))  # :228-229
             _raise_on(status)
         return logp, None, None
+
+    def train_forward(self, data, noise=None, generator=None):
+        """The reference's training forward (``EBGCN.py:61-93``, ``:223-230``) with autograd
+        throughout: ``(log_probs [B, num_class], TD_edge_loss, BU_edge_loss)``, whatever
+        ``self.training`` says for the BatchNorms (batch statistics, running statistics updated).
+        A direction whose ``edge_infer_*`` flag is off returns the loss ``None`` and runs conv2
+        without edge weights.  ``noise``: a pair ``(td, bu)`` of standard-normal draws ``[E, 64]``
+        for the two Bayesian branches (``None``: drawn from ``generator``).
+
+        This is plumbing, not a fast path: per direction it composes ``gcn_conv``,
+        :func:`bigcn_amd.ops.edge_infer_train`, ``torch.nn.functional.batch_norm`` over the dense
+        ``[N, 64 + F]`` concat, ``gcn_conv(..., edge_weight=edge_pred)`` and ``scatter_mean``;
+        only the edge inference is fused.  An index out of range raises ``IndexError`` at the end of
+        the call (one host sync); the BatchNorms have by then been updated from the valid part of
+        the batch (a direction without one valid edge leaves its per-edge norms untouched)."""
+        td_noise, bu_noise = (None, None) if noise is None else noise
+        status = torch.zeros(1, dtype=torch.int32, device=data.x.device)
+        td_x, td_loss = self.TDrumorGCN._train_encode(data, td_noise, generator, status)
+        bu_x, bu_loss = self.BUrumorGCN._train_encode(data, bu_noise, generator, status)
+        out = self.fc(torch.cat((bu_x, td_x), 1))                              # :227-228, BU first
+        _raise_on(status)
+        return torch.nn.functional.log_softmax(out, dim=1), td_loss, bu_loss   # :229-230
 
     # ---- the evaluation loop (EBGCN.py:328-354) as one native call per batch
     def _eval_tensors(self):

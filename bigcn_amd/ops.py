@@ -9,6 +9,8 @@
 * :func:`edge_infer` / :func:`ebgcn_conv2_lin` - what EBGCN's eval forward adds
   (``model/Twitter/EBGCN.py:72-116``): the edge-inference kernel and conv2's lin over the
   BatchNorm'd concat.
+* :func:`edge_infer_train` - the same edge inference in training mode (``EBGCN.py:95-116``):
+  batch-statistics BatchNorm, the Bayesian branch, the KL edge loss and the backward.
 * :func:`explain_sums` / :func:`segment_rank` - the reference's analysis (``explain_PHEME.py``):
   per-node stage sums without the concat, and a batched per-tree ``topk(k = n)``.
 * :func:`tree_centrality` / :func:`rank_similarity` - the reference's comparison
@@ -448,7 +450,8 @@ def scatter_mean(src: torch.Tensor, index: torch.Tensor, dim: int = 0, out=None,
 # ----------------------------------------------------------------------------- EBGCN (eval)
 EDGE_INFER_TILE = _lib.BGCN_EDGE_INFER_TILE   # edges per workgroup of the edge-inference kernel
 _NO_TRAINING = ("bigcn_amd's EBGCN is the inference-only path (eval mode): training - batch-statistics "
-                "BatchNorm, the Bayesian edge branch and its KL loss, the backward - is not implemented")
+                "BatchNorm, the Bayesian edge branch and its KL loss, the backward - is not implemented "
+                "by forward.  EBGCN.train_forward(data) is the training forward.")
 
 
 def bn_fold(bn: torch.nn.Module):
@@ -503,6 +506,149 @@ def edge_infer(h: torch.Tensor, edge_index: torch.Tensor, direction_module, vali
     if validate and int(status.item()) & 1:
         raise IndexError("edge_index contains an index out of range [0, num_nodes)")
     return pred
+
+
+# ----------------------------------------------------------------------------- EBGCN (training)
+EDGE_NETWORKS = ("sim_network", "W_mean", "W_bias", "B_mean", "B_bias")   # bgcn_edge_train_fwd_args.net order
+
+
+def _fill_edge_net(dst, tensors, eps) -> None:
+    dst.conv_w, dst.norm_weight, dst.norm_bias, dst.out_w, dst.out_b = (ptr(t) for t in tensors)
+    dst.eps = float(eps)
+
+
+class _EdgeInferTrainFn(torch.autograd.Function):
+    """``bgcn_edge_infer_train_fwd`` / ``_bwd``.  Inputs after ``meta``: h, the sim network's conv0
+    weight, norm0 weight and bias, conv_out weight and bias, fc1's weight (the seven that receive
+    a gradient), then the Bayesian networks' tensors, fc2's weight, the noise and the edge list."""
+
+    @staticmethod
+    def forward(ctx, meta, h, wc, gamma, beta, wo, bo, fc1, *rest):
+        bayes, (fc2, noise, ei) = rest[:20], rest[20:]
+        eps, status = meta["eps"], meta["status"]
+        dev = h.device
+        hc = _f32c(h)
+        N, E, K = int(hc.size(0)), int(ei.size(1)), int(fc1.size(0))
+        held = [_f32c(t) for t in (wc, gamma, beta, wo, bo, fc1, fc2) + tuple(bayes)]
+        sim, f1, f2, bay = held[:5], held[5], held[6], held[7:]
+        f32 = dict(dtype=torch.float32, device=dev)
+        pred, loss = torch.empty(E, **f32), torch.empty(1, **f32)
+        s, p, py = torch.empty(E, 64, **f32), torch.empty(E, K, **f32), torch.empty(E, K, **f32)
+        sim_stats = torch.empty(2, 64, **f32)
+        nvalid = torch.empty(1, dtype=torch.int32, device=dev)
+        bmean, bvar = torch.empty(5, 64, **f32), torch.empty(5, 64, **f32)
+        a = _lib.EdgeTrainFwdArgs()
+        a.h, a.ldh, a.num_nodes, a.hid = hc.data_ptr(), hc.stride(0), N, int(hc.size(1))
+        a.edge_index, a.num_edges = ei.data_ptr(), E
+        _fill_edge_net(a.net[0], sim, eps[0])
+        for n in range(4):
+            _fill_edge_net(a.net[n + 1], bay[5 * n:5 * n + 5], eps[n + 1])
+        a.fc1_w, a.fc2_w, a.edge_num, a.noise = f1.data_ptr(), f2.data_ptr(), K, noise.data_ptr()
+        a.edge_pred, a.edge_loss, a.s, a.p, a.p_y = (t.data_ptr() for t in (pred, loss, s, p, py))
+        a.sim_mean, a.sim_rstd, a.num_valid = sim_stats[0].data_ptr(), sim_stats[1].data_ptr(), nvalid.data_ptr()
+        a.batch_mean, a.batch_var, a.status = bmean.data_ptr(), bvar.data_ptr(), status.data_ptr()
+        L = _lib.lib()
+        ws = workspace(L.bgcn_edge_infer_train_workspace_size(N, E), dev)
+        check(L.bgcn_edge_infer_train_fwd(ctypes.addressof(a), ws.data_ptr(), ws.numel(), stream_handle()))
+        ctx.save_for_backward(hc, ei, sim[0], sim[1], sim[2], sim[3], f1, s, p, py, sim_stats, nvalid)
+        ctx.eps = eps[0]
+        ctx.in_dtypes = tuple(t.dtype for t in (h, wc, gamma, beta, wo, bo, fc1))
+        meta["batch_mean"], meta["batch_var"], meta["num_valid"] = bmean, bvar, nvalid
+        return loss.view(()), pred
+
+    @staticmethod
+    def backward(ctx, d_loss, d_pred):
+        hc, ei, wc, gamma, beta, wo, f1, s, p, py, sim_stats, nvalid = ctx.saved_tensors
+        dev = hc.device
+        N, E, K = int(hc.size(0)), int(ei.size(1)), int(f1.size(0))
+        d_loss, d_pred = _f32c(d_loss).view(1), _f32c(d_pred)
+        f32 = dict(dtype=torch.float32, device=dev)
+        dh, dwc = torch.empty(N, 64, **f32), torch.empty(64, 64, **f32)
+        dgamma, dbeta, dwo, dbo = (torch.empty(n, **f32) for n in (64, 64, 64, 1))
+        df1 = torch.empty(K, 64, **f32)
+        a = _lib.EdgeTrainBwdArgs()
+        a.h, a.ldh, a.num_nodes, a.hid = hc.data_ptr(), hc.stride(0), N, 64
+        a.edge_index, a.num_edges = ei.data_ptr(), E
+        _fill_edge_net(a.sim, (wc, gamma, beta, wo, None), ctx.eps)
+        a.fc1_w, a.edge_num = f1.data_ptr(), K
+        a.s, a.p, a.p_y = s.data_ptr(), p.data_ptr(), py.data_ptr()
+        a.sim_mean, a.sim_rstd, a.num_valid = sim_stats[0].data_ptr(), sim_stats[1].data_ptr(), nvalid.data_ptr()
+        a.d_pred, a.d_loss = d_pred.data_ptr(), d_loss.data_ptr()
+        a.d_h, a.ldd = dh.data_ptr(), 64
+        a.d_conv_w, a.d_norm_weight, a.d_norm_bias = dwc.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()
+        a.d_out_w, a.d_out_b, a.d_fc1_w = dwo.data_ptr(), dbo.data_ptr(), df1.data_ptr()
+        L = _lib.lib()
+        ws = workspace(L.bgcn_edge_infer_train_workspace_size(N, E), dev)
+        check(L.bgcn_edge_infer_train_bwd(ctypes.addressof(a), ws.data_ptr(), ws.numel(), stream_handle()))
+        # (the passes share their recomputation: all seven are always computed)
+        grads = (dh, dwc.view(64, 64, 1), dgamma, dbeta, dwo.view(1, 64, 1), dbo, df1)
+        grads = tuple(g.to(dt) if need else None
+                      for g, dt, need in zip(grads, ctx.in_dtypes, ctx.needs_input_grad[1:8]))
+        return (None,) + grads + (None,) * 23
+
+
+def edge_infer_train(h: torch.Tensor, edge_index: torch.Tensor, direction_module, noise: Optional[torch.Tensor] = None,
+                     generator: Optional[torch.Generator] = None, status: Optional[torch.Tensor] = None):
+    """``(edge_loss, edge_pred)`` of ``direction_module.edge_infer(h, edge_index)`` in TRAINING mode
+    (``EBGCN.py:95-116``, ``:189-212``) as one autograd function on ``bgcn_edge_infer_train_fwd`` /
+    ``_bwd``: the five per-edge networks with batch-statistics BatchNorm, fc1 -> sigmoid -> mean
+    (``edge_pred`` [E]), the Bayesian draw and the KL edge loss (0-dim).
+
+    Gradients reach ``h``, the sim network's five parameters and ``fc1.weight`` only: the
+    reference's ``th.normal`` has no gradient, so the four Bayesian networks and ``fc2`` get none
+    (their ``.grad`` stays ``None``).  All five ``norm0`` modules have their running statistics and
+    ``num_batches_tracked`` updated as ``torch.nn.BatchNorm1d`` does in training.
+
+    ``noise``: the standard-normal draw, fp32 ``[E, 64]`` (``y = sigmoid(mean + std * noise)``);
+    ``None`` draws ``torch.randn`` on the device from ``generator``.  An edge with an index outside
+    [0, N) gets ``edge_pred`` 0, adds to no statistic, loss or gradient and sets ``status`` (int32
+    [1], optional) to 1.  ``E == 0`` raises ``ValueError``."""
+    nets = [getattr(direction_module, n) for n in EDGE_NETWORKS]
+    fc1, fc2 = direction_module.fc1.weight, direction_module.fc2.weight
+    norms = [net[1] for net in nets]
+    for bn in norms:
+        if bn.momentum is None:
+            raise ValueError("edge_infer_train: BatchNorm momentum=None (cumulative average) is not supported")
+        if bn.running_mean is None or bn.weight is None:
+            raise ValueError("edge_infer_train needs affine BatchNorms with running statistics")
+    _dev_check(h, edge_index, fc1, fc2, noise)
+    ei = _check_ei(edge_index)
+    E = int(ei.size(1))
+    if E == 0:
+        raise ValueError("edge_infer_train needs at least one edge (BatchNorm has no batch to take statistics of)")
+    if h.dim() != 2 or h.size(1) != 64:
+        raise ValueError("h must be [N, 64]")
+    K = int(fc1.size(0))
+    if fc1.shape != (K, 64) or fc2.shape != (K, 64) or not 1 <= K <= 8:
+        raise ValueError("fc1 / fc2 must be [edge_num, 64] with edge_num in [1, 8]")
+    for net in nets:
+        if net[0].weight.shape != (64, 64, 1) or net[3].weight.shape != (1, 64, 1):
+            raise ValueError("the per-edge networks do not match the hidden size 64")
+    if noise is None:
+        noise = torch.randn(E, 64, dtype=torch.float32, device=h.device, generator=generator)
+    elif noise.shape != (E, 64):
+        raise ValueError("noise must be [E, 64]")
+    noise = _f32c(noise)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=h.device)
+    meta = {"eps": [float(bn.eps) for bn in norms], "status": status}
+
+    def tensors(net):
+        return (net[0].weight, net[1].weight, net[1].bias, net[3].weight, net[3].bias)
+
+    bayes = [t.detach() for net in nets[1:] for t in tensors(net)]
+    loss, pred = _EdgeInferTrainFn.apply(meta, h, *tensors(nets[0]), fc1, *bayes, fc2.detach(), noise, ei)
+    with torch.no_grad():
+        # a batch without one valid edge has no statistics: it blends nothing (decided on the
+        # device, no sync)
+        some = meta["num_valid"] > 0
+        for n, bn in enumerate(norms):
+            m = some.to(bn.running_mean.dtype) * float(bn.momentum)
+            bn.running_mean.add_(m * (meta["batch_mean"][n].to(bn.running_mean.dtype) - bn.running_mean))
+            bn.running_var.add_(m * (meta["batch_var"][n].to(bn.running_var.dtype) - bn.running_var))
+            if bn.num_batches_tracked is not None:
+                bn.num_batches_tracked += some.to(bn.num_batches_tracked.dtype).view(())
+    return loss, pred
 
 
 def ebgcn_conv2_lin(h1: torch.Tensor, x: torch.Tensor, batch: torch.Tensor, rootindex: torch.Tensor,

@@ -769,6 +769,90 @@ int bgcn_ebgcn_eval_saved(void* workspace, size_t workspace_bytes, int64_t num_n
                           int dir, bgcn_ebgcn_eval_view* out);
 
 /* --------------------------------------------------------------------------
+ * EBGCN edge inference in TRAINING mode: TDrumorGCN.edge_infer / BUrumorGCN.edge_infer
+ * (model/Twitter/EBGCN.py:95-116, :189-212) with batch-statistics BatchNorm, the Bayesian branch,
+ * the KL edge loss, and the backward.  Additive entry points: BGCN_ABI_VERSION is unchanged.
+ *
+ * Per edge e, a = h[(row_e - 1) mod N], b = h[(col_e - 1) mod N] (the reference's indexing, as
+ * bgcn_edge_infer), D[c][l] = |a[c] - b[l]|.  Each network n of net[] = { sim_network, W_mean,
+ * W_bias, B_mean, B_bias }:
+ *   Y_n[e][o][l] = sum_c conv_w[o][c] D[e][c][l]
+ *   mu_n[o], v_n[o] = mean and biased variance of Y_n[.][o][.] over the n_el = 64 E_valid values
+ *   Z = leaky_relu(norm_weight (Y - mu) / sqrt(v + eps) + norm_bias, 0.01)
+ *   out_n[e][l] = sum_o out_w[o] Z[e][o][l] + out_b
+ * and with s = out_sim:
+ *   p[e][k] = sigmoid(sum_l fc1[k][l] s[e][l]);  edge_pred[e] = mean_k p[e][k]
+ *   y = sigmoid(out_Wmean s + out_Bmean + relu(log(s^2 exp(out_Wbias) + exp(out_Bbias))) noise)
+ *   p_y = softmax_k(fc2 y);  edge_loss = (1 / E_valid) sum_e sum_k p_y (log p_y - log_softmax_k(p))
+ * batch_mean / batch_var [5, 64] receive mu_n and the UNBIASED variance v_n n_el / (n_el - 1):
+ * what torch.nn.BatchNorm1d blends into its running statistics (the caller does the blend).
+ * The variance is two-pass: the mean is formed first (mu = conv_w . mean(D)), the pass that sums
+ * squares sums them of centred values, and block partials are merged in fp64.
+ *
+ * p_y is a constant target (the reference's th.normal has no gradient): the backward reaches h,
+ * the sim network's five parameters and fc1 only.  It takes d_pred [E] and d_loss [1] (device)
+ * and the tensors the forward saved (s [E, 64], p and p_y [E, edge_num], sim_mean and sim_rstd
+ * [64], num_valid [1]) and OVERWRITES d_h [N, ldd >= 64] and the six parameter gradients.
+ *
+ * Y is a 64 x 64 x 64 product per edge and network on the fp32 MFMA and is never stored: the
+ * forward computes it twice (statistics, apply), the backward three times.  Deterministic: no
+ * float atomics; cross-block sums go through block partials in the workspace and a fixed-order
+ * second step, d_h is an ordered per-node sum over a counting sort of the 2 E edge ends.
+ * An edge with an end outside [0, N) reads nothing, adds to no sum, gets edge_pred 0 and sets
+ * bit 0 of *status (the forward does not zero *status).
+ *
+ * BGCN_EINVAL before any HIP call: hid != 64 ("hidden size must be 64"), edge_num outside [1, 8]
+ * ("edge_num"), num_edges <= 0 ("at least one edge"), h not 16-byte aligned or ldh % 4 != 0, a
+ * null pointer, "workspace too small".  One workspace size serves both calls; 0 = bad sizes.
+ * -------------------------------------------------------------------------- */
+typedef struct bgcn_edge_net {     /* one per-edge network (create_network, EBGCN.py:33-46), fp32 */
+  const float* conv_w;             /* <name>conv0.weight [64, 64]                  */
+  const float* norm_weight;        /* <name>norm0.weight [64]                      */
+  const float* norm_bias;          /* <name>norm0.bias [64]                        */
+  const float* out_w;              /* <name>conv_out.weight [64]                   */
+  const float* out_b;              /* <name>conv_out.bias [1]                      */
+  float eps;                       /* <name>norm0.eps                              */
+} bgcn_edge_net;
+typedef struct bgcn_edge_train_fwd_args {
+  const float* h; int64_t ldh;     /* conv1's output [N, ldh >= 64]                */
+  int64_t num_nodes; int64_t hid;  /* hid == 64                                    */
+  const int64_t* edge_index; int64_t num_edges;   /* [2, E], E > 0                 */
+  bgcn_edge_net net[5];            /* sim_network, W_mean, W_bias, B_mean, B_bias  */
+  const float* fc1_w; const float* fc2_w;         /* [edge_num, 64] each           */
+  int32_t edge_num;                /* in [1, 8]                                    */
+  const float* noise;              /* [E, 64] the standard-normal draw             */
+  float* edge_pred;                /* [E]                                          */
+  float* edge_loss;                /* [1]                                          */
+  float* s; float* p; float* p_y;  /* saved: [E, 64], [E, edge_num] x 2            */
+  float* sim_mean; float* sim_rstd;   /* saved: [64] each, the sim network's       */
+  int32_t* num_valid;              /* saved: [1] edges with both ends in range     */
+  float* batch_mean; float* batch_var;   /* [5, 64] each (unbiased variance)       */
+  int32_t* status;                 /* [1]                                          */
+} bgcn_edge_train_fwd_args;
+typedef struct bgcn_edge_train_bwd_args {
+  const float* h; int64_t ldh;
+  int64_t num_nodes; int64_t hid;
+  const int64_t* edge_index; int64_t num_edges;
+  bgcn_edge_net sim;               /* out_b is not read                            */
+  const float* fc1_w;
+  int32_t edge_num;
+  const float* s; const float* p; const float* p_y;
+  const float* sim_mean; const float* sim_rstd;
+  const int32_t* num_valid;
+  const float* d_pred;             /* [E]                                          */
+  const float* d_loss;             /* [1]                                          */
+  float* d_h; int64_t ldd;         /* [N, ldd >= 64]                               */
+  float* d_conv_w; float* d_norm_weight; float* d_norm_bias;   /* [64, 64], [64], [64] */
+  float* d_out_w; float* d_out_b;  /* [64], [1]                                    */
+  float* d_fc1_w;                  /* [edge_num, 64]                               */
+} bgcn_edge_train_bwd_args;
+size_t bgcn_edge_infer_train_workspace_size(int64_t num_nodes, int64_t num_edges);
+int bgcn_edge_infer_train_fwd(const bgcn_edge_train_fwd_args* args, void* workspace, size_t workspace_bytes,
+                              bgcn_stream_t stream);
+int bgcn_edge_infer_train_bwd(const bgcn_edge_train_bwd_args* args, void* workspace, size_t workspace_bytes,
+                              bgcn_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * Optimiser step of the training loop: torch.optim.Adam with the reference's three
  * parameter groups (BiGCN_Twitter.py:146-153, step at :189) as ONE fused launch.
  * amsgrad = False; weight_decay is L2 added to the gradient (torch Adam semantics).
