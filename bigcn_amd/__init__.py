@@ -8,7 +8,9 @@ Drop-in symbols for the reference's hot path (cwkd/BiGCN):
 * ``EBGCN`` - the edge-enhanced model (model/Twitter/EBGCN.py): eval forward on the edge-inference
   kernel (``edge_infer``), reference checkpoints load strictly; ``EBGCN.train_forward`` is the
   reference's training forward with autograd, on ``edge_infer_train`` (the five per-edge networks
-  with batch-statistics BatchNorm, the Bayesian branch, the KL edge loss and their backward)
+  with batch-statistics BatchNorm, the Bayesian branch, the KL edge loss and their backward) and
+  ``ebgcn_conv2_lin_train`` (batch-statistics bn1 + relu + conv2's lin and their backward without the
+  dense [N, 64 + F] concat) followed by ``gcn_aggregate`` (the aggregation half of ``gcn_conv``)
 * ``explain`` / ``segment_rank`` - the reference's analysis (explain_PHEME.py): per-stage node sums and
   per-tree rankings of a whole batch, for ``BiGCN`` / ``Net`` / ``EBGCN`` in eval mode
 * ``compare`` / ``tree_centrality`` / ``rank_similarity`` - the reference's comparison
@@ -30,13 +32,15 @@ from .ebgcn import EBGCN
 from .explain import explain, segment_rank
 from . import metrics
 from .metrics import EpochMetrics, class_metrics, confusion, evaluation4class, evaluationclass
-from .ops import Graph, bigcn_encoder, build_graph, edge_infer, edge_infer_train, gcn_conv, scatter_mean, spmm
+from .ops import (Graph, bigcn_encoder, build_graph, ebgcn_conv2_lin_train, edge_infer, edge_infer_train,
+                  gcn_aggregate, gcn_conv, scatter_mean, spmm)
 from .optim import FusedAdam, bigcn_adam
 from .train import FusedTrainStep
 
 __all__ = ["GCNConv", "scatter_mean", "TDrumorGCN", "BUrumorGCN", "BiGCN", "Net", "make_optimizer",
            "Graph", "build_graph", "gcn_conv", "spmm", "bigcn_encoder", "FusedAdam", "bigcn_adam",
-           "FusedTrainStep", "EBGCN", "edge_infer", "edge_infer_train", "explain", "segment_rank",
+           "FusedTrainStep", "EBGCN", "edge_infer", "edge_infer_train", "ebgcn_conv2_lin_train", "gcn_aggregate",
+           "explain", "segment_rank",
            "compare", "tree_centrality", "rank_similarity",
            "metrics", "confusion", "class_metrics", "evaluation4class", "evaluationclass", "EpochMetrics"]
 __version__ = "0.1.0"

@@ -67,6 +67,7 @@ EXPORTED_SYMBOLS = (
     "bgcn_rank_similarity", "bgcn_confusion",
     "bgcn_ebgcn_eval_workspace_size", "bgcn_ebgcn_eval_step", "bgcn_ebgcn_eval_saved",
     "bgcn_edge_infer_train_workspace_size", "bgcn_edge_infer_train_fwd", "bgcn_edge_infer_train_bwd",
+    "bgcn_ebgcn_conv2_lin_train_workspace_size", "bgcn_ebgcn_conv2_lin_train_fwd", "bgcn_ebgcn_conv2_lin_train_bwd",
 )
 
 
@@ -203,6 +204,31 @@ class EdgeTrainBwdArgs(Structure):
     ]
 
 
+class Conv2LinTrainFwdArgs(Structure):
+    """bgcn_conv2_lin_train_fwd_args (include/bgcn.h)."""
+    _fields_ = [
+        ("h1", c_void_p), ("ldh", c_int64), ("x", c_void_p), ("ldx", c_int64),
+        ("batch", c_void_p), ("rootindex", c_void_p),
+        ("num_nodes", c_int64), ("num_graphs", c_int64), ("in_feats", c_int64), ("hid", c_int64),
+        ("w2", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("eps", c_float),
+        ("z2", c_void_p), ("ldz", c_int64), ("batch_mean", c_void_p), ("batch_var", c_void_p),
+        ("bn_g", c_void_p), ("bn_t", c_void_p), ("a_x", c_void_p),
+        ("tree_count", c_void_p), ("num_valid", c_void_p), ("status", c_void_p),
+    ]
+
+
+class Conv2LinTrainBwdArgs(Structure):
+    """bgcn_conv2_lin_train_bwd_args (include/bgcn.h)."""
+    _fields_ = [
+        ("dz2", c_void_p), ("lddz", c_int64), ("h1", c_void_p), ("ldh", c_int64), ("x", c_void_p), ("ldx", c_int64),
+        ("batch", c_void_p), ("rootindex", c_void_p),
+        ("num_nodes", c_int64), ("num_graphs", c_int64), ("in_feats", c_int64), ("hid", c_int64),
+        ("w2", c_void_p), ("eps", c_float), ("batch_mean", c_void_p), ("batch_var", c_void_p),
+        ("bn_g", c_void_p), ("bn_t", c_void_p), ("a_x", c_void_p), ("tree_count", c_void_p), ("num_valid", c_void_p),
+        ("dh1", c_void_p), ("ldd", c_int64), ("dw2", c_void_p), ("dgamma", c_void_p), ("dbeta", c_void_p),
+    ]
+
+
 _SIGS = {
     "bgcn_abi_version": (c_int, []),
     "bgcn_last_error": (c_char_p, []),
@@ -302,6 +328,9 @@ _SIGS = {
     "bgcn_edge_infer_train_workspace_size": (c_size_t, [c_int64, c_int64]),
     "bgcn_edge_infer_train_fwd": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_edge_infer_train_bwd": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "bgcn_ebgcn_conv2_lin_train_workspace_size": (c_size_t, [c_int64, c_int64, c_int64]),
+    "bgcn_ebgcn_conv2_lin_train_fwd": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "bgcn_ebgcn_conv2_lin_train_bwd": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

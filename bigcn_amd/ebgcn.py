@@ -30,8 +30,8 @@ from . import _lib
 from ._lib import check, ptr, stream_handle
 from .bigcn import _num_graphs
 from .conv import GCNConv
-from .ops import (_NO_TRAINING, _check_ei, _i64c, build_graph, degree_code, ebgcn_conv2_lin, edge_infer,
-                  edge_infer_train, gcn_conv, scatter_mean, spmm)
+from .ops import (_NO_TRAINING, _check_ei, _i64c, build_graph, degree_code, ebgcn_conv2_lin, ebgcn_conv2_lin_train,
+                  edge_infer, edge_infer_train, gcn_aggregate, gcn_conv, scatter_mean, spmm)
 
 
 def _edge_network(hidden: int, name: str) -> torch.nn.Sequential:
@@ -86,7 +86,8 @@ class _EdgeRumorGCN(torch.nn.Module):
 
     def _train_encode(self, data, noise, generator, status):
         """The training forward of one direction (``:61-93``) with autograd: ``(x [B, 128],
-        edge_loss or None)``.  The ``[N, 64 + F]`` concat is kept dense."""
+        edge_loss or None)``.  The ``[N, 64 + F]`` concat is never formed (a one-node batch, whose bn1
+        the reference skips, keeps the torch composition)."""
         x = data.x.float()
         ei = getattr(data, self.edge_key)
         batch, rootindex = data.batch, data.rootindex
@@ -96,18 +97,15 @@ class _EdgeRumorGCN(torch.nn.Module):
         if bool(getattr(self.args, self.infer_flag)):                          # :67-70
             edge_loss, edge_pred = edge_infer_train(h1, ei, self, noise=noise, generator=generator, status=status)
         root_of_node = rootindex[batch]
-        cat = torch.cat((h1, x.index_select(0, root_of_node)), 1)              # :72-78
-        if N != 1:                                                             # :80-81, batch statistics
-            bn = self.bn1
-            factor = 0.0
-            if bn.track_running_stats and bn.num_batches_tracked is not None:
-                bn.num_batches_tracked += 1
-                factor = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else bn.momentum
-            cat = torch.nn.functional.batch_norm(cat, bn.running_mean, bn.running_var, bn.weight, bn.bias, True,
-                                                 factor, bn.eps)
-        cat = torch.relu(cat)                                                  # :82
-        h2 = gcn_conv(cat, ei, self.conv2.lin.weight, self.conv2.bias, edge_weight=edge_pred,
-                      degree_on=self.conv2.degree_on)                          # :84
+        if N != 1:
+            # :72-84 cat, bn1 on batch statistics, relu and conv2's lin without the concat, then conv2's
+            # aggregation
+            z2 = ebgcn_conv2_lin_train(h1, x, batch, rootindex, self.conv2.lin.weight, self.bn1, status=status)
+            h2 = gcn_aggregate(z2, ei, self.conv2.bias, edge_weight=edge_pred, degree_on=self.conv2.degree_on)
+        else:                                                                  # :80-81, bn1 skipped
+            cat = torch.relu(torch.cat((h1, x.index_select(0, root_of_node)), 1))
+            h2 = gcn_conv(cat, ei, self.conv2.lin.weight, self.conv2.bias, edge_weight=edge_pred,
+                          degree_on=self.conv2.degree_on)                      # :84
         # :65 x2 = copy.copy(x) is a copy outside the autograd graph: as in the reference, no
         # gradient reaches conv1 through the root rows of the readout (:86-90)
         h = torch.cat((torch.relu(h2), h1.detach().index_select(0, root_of_node)), 1)
@@ -202,10 +200,11 @@ class EBGCN(torch.nn.Module):
         without edge weights.  ``noise``: a pair ``(td, bu)`` of standard-normal draws ``[E, 64]``
         for the two Bayesian branches (``None``: drawn from ``generator``).
 
-        This is plumbing, not a fast path: per direction it composes ``gcn_conv``,
-        :func:`bigcn_amd.ops.edge_infer_train`, ``torch.nn.functional.batch_norm`` over the dense
-        ``[N, 64 + F]`` concat, ``gcn_conv(..., edge_weight=edge_pred)`` and ``scatter_mean``;
-        only the edge inference is fused.  An index out of range raises ``IndexError`` at the end of
+        Per direction it composes ``gcn_conv`` (conv1), :func:`bigcn_amd.ops.edge_infer_train` (fused),
+        :func:`bigcn_amd.ops.ebgcn_conv2_lin_train` (fused: batch-statistics bn1, relu and conv2's lin
+        without the dense ``[N, 64 + F]`` concat), :func:`bigcn_amd.ops.gcn_aggregate` with
+        ``edge_weight=edge_pred`` and ``scatter_mean``; conv1, the readout and the optimiser are
+        separate calls, a one-call EBGCN step is not built.  An index out of range raises ``IndexError`` at the end of
         the call (one host sync); the BatchNorms have by then been updated from the valid part of
         the batch (a direction without one valid edge leaves its per-edge norms untouched)."""
         td_noise, bu_noise = (None, None) if noise is None else noise

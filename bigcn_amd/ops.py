@@ -11,6 +11,9 @@
   BatchNorm'd concat.
 * :func:`edge_infer_train` - the same edge inference in training mode (``EBGCN.py:95-116``):
   batch-statistics BatchNorm, the Bayesian branch, the KL edge loss and the backward.
+* :func:`ebgcn_conv2_lin_train` / :func:`gcn_aggregate` - conv2 of the training forward
+  (``EBGCN.py:72-84``): batch-statistics bn1 + relu + conv2's lin and their backward without the dense
+  concat, then the aggregation half of :func:`gcn_conv`.
 * :func:`explain_sums` / :func:`segment_rank` - the reference's analysis (``explain_PHEME.py``):
   per-node stage sums without the concat, and a batched per-tree ``topk(k = n)``.
 * :func:`tree_centrality` / :func:`rank_similarity` - the reference's comparison
@@ -320,6 +323,41 @@ def _linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def _aggregate(g: Graph, z: torch.Tensor, bias, O: int) -> torch.Tensor:
+    """``A_hat z + b`` for z of padded width; the first O columns, contiguous."""
+    b = None if bias is None else _pad4(bias.view(1, -1)).view(-1)
+    return spmm(g, z, b)[:, :O].contiguous()
+
+
+def _aggregate_backward(g: Graph, dout: torch.Tensor, z, ei, degree_on: str, need_bias: bool):
+    """The aggregation's backward: ``(A_hat^T dout`` of padded width, ``d edge_weight`` or None, ``d bias`` or
+    None``)``.  ``z`` / ``ei`` (the padded aggregation input and the edge list) are given when the edge
+    weights are learned."""
+    L = _lib.lib()
+    N, O = dout.shape
+    d = _pad4(dout.float())
+    dzp = spmm(g, d, transposed=True)                       # A_hat^T dout (padded width)
+    dew = db = None
+    if z is not None:
+        # gcn_norm's backward (EBGCN.py:84,178 learn edge_weight): row dots of
+        # (dout, A_hat h) and (h, A_hat^T dout), then one dot per edge
+        agg = spmm(g, z)                                     # A_hat h, no bias
+        E = int(ei.size(1))
+        dew = torch.empty(E, dtype=torch.float32, device=dout.device)
+        ws = workspace(L.bgcn_edge_weight_grad_workspace_size(N), dout.device)
+        F4 = int(z.size(1))
+        check(L.bgcn_edge_weight_grad(ptr(ei), E, N, degree_code(degree_on), _graph_dinv(g), ptr(z),
+                                      ptr(agg), ptr(d), ptr(dzp), F4, F4, ptr(dew), ptr(ws), ws.numel(),
+                                      stream_handle()))
+    if need_bias:
+        db = torch.empty(O, dtype=torch.float32, device=dout.device)
+        dd = dout.float().contiguous()
+        ws = workspace(L.bgcn_colsum_workspace_size(N, O), dout.device)
+        check(L.bgcn_colsum(ptr(dd), dd.stride(0), N, O, ptr(db), ptr(ws), ws.numel(),
+                            stream_handle()))
+    return dzp, dew, db
+
+
 class _GCNConvFn(torch.autograd.Function):
     """PyG-2.x GCNConv: out = A_hat (x W^T) + b, A_hat = gcn_norm(edge_index, edge_weight)."""
 
@@ -328,39 +366,26 @@ class _GCNConvFn(torch.autograd.Function):
         x = x.contiguous().float()
         weight = weight.contiguous()
         z = _pad4(_linear(x, weight))
-        O = weight.size(0)
-        b = None if bias is None else _pad4(bias.view(1, -1)).view(-1)
-        out = spmm(g, z, b)[:, :O]
+        out = _aggregate(g, z, bias, weight.size(0))
         ctx.g = g
         ctx.degree_on = degree_on
         ew_grad = edge_weight is not None and ctx.needs_input_grad[5]
         # the edge-weight gradient needs h = x W^T (padded) and the edge list
         ctx.save_for_backward(x, weight, z if ew_grad else None, edge_index if ew_grad else None)
         ctx.has_bias = bias is not None
-        return out.contiguous()
+        return out
 
     @staticmethod
     def backward(ctx, dout):
         x, weight, z, ei = ctx.saved_tensors
-        g: Graph = ctx.g
         L = _lib.lib()
         N, K = x.shape
         O = weight.size(0)
-        d = _pad4(dout.float())
-        dzp = spmm(g, d, transposed=True)                       # A_hat^T dout (padded width)
+        ew_grad = len(ctx.needs_input_grad) > 5 and ctx.needs_input_grad[5] and z is not None
+        dzp, dew, db = _aggregate_backward(ctx.g, dout, z if ew_grad else None, ei, ctx.degree_on,
+                                           ctx.has_bias and ctx.needs_input_grad[2])
         dz = dzp[:, :O].contiguous()
-        dx = dw = db = dew = None
-        if len(ctx.needs_input_grad) > 5 and ctx.needs_input_grad[5] and z is not None:
-            # gcn_norm's backward (EBGCN.py:84,178 learn edge_weight): row dots of
-            # (dout, A_hat h) and (h, A_hat^T dout), then one dot per edge
-            agg = spmm(g, z)                                     # A_hat h, no bias
-            E = int(ei.size(1))
-            dew = torch.empty(E, dtype=torch.float32, device=x.device)
-            ws = workspace(L.bgcn_edge_weight_grad_workspace_size(N), x.device)
-            F4 = int(z.size(1))
-            check(L.bgcn_edge_weight_grad(ptr(ei), E, N, degree_code(ctx.degree_on), _graph_dinv(g), ptr(z),
-                                          ptr(agg), ptr(d), ptr(dzp), F4, F4, ptr(dew), ptr(ws), ws.numel(),
-                                          stream_handle()))
+        dx = dw = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(N, K, dtype=torch.float32, device=x.device)
             check(L.bgcn_gemm_xw(ptr(dz), dz.stride(0), ptr(weight), weight.stride(0), ptr(dx), K,
@@ -370,32 +395,71 @@ class _GCNConvFn(torch.autograd.Function):
             ws = workspace(L.bgcn_gemm_tn_workspace_size(O, K, N), x.device)
             check(L.bgcn_gemm_tn(ptr(dz), dz.stride(0), ptr(x), x.stride(0), ptr(dw), 0, K, O, O, K,
                                  N, ptr(ws), ws.numel(), stream_handle()))
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = torch.empty(O, dtype=torch.float32, device=x.device)
-            dd = dout.float().contiguous()
-            ws = workspace(L.bgcn_colsum_workspace_size(N, O), x.device)
-            check(L.bgcn_colsum(ptr(dd), dd.stride(0), N, O, ptr(db), ptr(ws), ws.numel(),
-                                stream_handle()))
         return (dx, dw, db, None, None, dew, None)[:len(ctx.needs_input_grad)]
+
+
+class _GCNAggregateFn(torch.autograd.Function):
+    """The aggregation half of :class:`_GCNConvFn`: out = A_hat z + b."""
+
+    @staticmethod
+    def forward(ctx, z, bias, g: Graph, edge_index=None, edge_weight=None, degree_on="col"):
+        O = z.size(1)
+        zp = _pad4(z.float())
+        out = _aggregate(g, zp, bias, O)
+        ctx.g = g
+        ctx.degree_on = degree_on
+        ew_grad = edge_weight is not None and ctx.needs_input_grad[4]
+        ctx.save_for_backward(zp if ew_grad else None, edge_index if ew_grad else None)
+        ctx.has_bias = bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        zp, ei = ctx.saved_tensors
+        O = dout.size(1)
+        ew_grad = len(ctx.needs_input_grad) > 4 and ctx.needs_input_grad[4] and zp is not None
+        dzp, dew, db = _aggregate_backward(ctx.g, dout, zp if ew_grad else None, ei, ctx.degree_on,
+                                           ctx.has_bias and ctx.needs_input_grad[1])
+        dz = dzp[:, :O].contiguous() if ctx.needs_input_grad[0] else None
+        return (dz, db, None, None, dew, None)[:len(ctx.needs_input_grad)]
+
+
+def _conv_graph(g, num_nodes: int, edge_weight, degree_on: str, what: str):
+    """``(graph, extra)`` for a convolution given an edge list or a :class:`Graph`: ``extra`` =
+    ``(edge_index, edge_weight, degree_on)`` when the edge weights are learned (gcn_norm's backward,
+    EBGCN.py:101-102 -> :84,178), else ``()``."""
+    if edge_weight is not None and edge_weight.requires_grad and torch.is_grad_enabled():
+        if isinstance(g, Graph):
+            raise ValueError(f"{what}: a learned edge_weight needs edge_index (the graph is built from it)")
+        ei = _check_ei(g)
+        if edge_weight.dim() != 1 or edge_weight.numel() != ei.size(1):
+            raise ValueError("edge_weight must be [E]")
+        return build_graph(ei, num_nodes, edge_weight.detach(), degree_on), (ei, edge_weight, degree_on)
+    if not isinstance(g, Graph):
+        g = build_graph(g, num_nodes, edge_weight, degree_on)
+    return g, ()
 
 
 def gcn_conv(x: torch.Tensor, edge_index_or_graph, weight: torch.Tensor,
              bias: Optional[torch.Tensor] = None, edge_weight: Optional[torch.Tensor] = None,
              degree_on: str = "col") -> torch.Tensor:
     _dev_check(x, weight, bias, edge_weight)
-    g = edge_index_or_graph
-    if edge_weight is not None and edge_weight.requires_grad and torch.is_grad_enabled():
-        # EBGCN (EBGCN.py:101-102 -> :84,178) learns its edge weights: gcn_norm's backward
-        if isinstance(g, Graph):
-            raise ValueError("gcn_conv: a learned edge_weight needs edge_index (the graph is built from it)")
-        ei = _check_ei(g)
-        if edge_weight.dim() != 1 or edge_weight.numel() != ei.size(1):
-            raise ValueError("edge_weight must be [E]")
-        g = build_graph(ei, x.size(0), edge_weight.detach(), degree_on)
-        return _GCNConvFn.apply(x, weight, bias, g, ei, edge_weight, degree_on)
-    if not isinstance(g, Graph):
-        g = build_graph(g, x.size(0), edge_weight, degree_on)
-    return _GCNConvFn.apply(x, weight, bias, g)
+    g, extra = _conv_graph(edge_index_or_graph, x.size(0), edge_weight, degree_on, "gcn_conv")
+    return _GCNConvFn.apply(x, weight, bias, g, *extra)
+
+
+def gcn_aggregate(z: torch.Tensor, edge_index_or_graph, bias: Optional[torch.Tensor] = None,
+                  edge_weight: Optional[torch.Tensor] = None, degree_on: str = "col") -> torch.Tensor:
+    """The aggregation half of :func:`gcn_conv`: ``A_hat z + bias`` with ``A_hat = gcn_norm(edge_index,
+    edge_weight)``, for a ``z = x W^T`` [N, O] computed elsewhere.  Gradients reach ``z``, ``bias`` and a
+    learned ``edge_weight``; given ``z`` from the same product, the result has ``gcn_conv``'s bits."""
+    _dev_check(z, bias, edge_weight)
+    if z.dim() != 2:
+        raise ValueError("z must be [N, O]")
+    if bias is not None and bias.numel() != z.size(1):
+        raise ValueError("bias must have O elements")
+    g, extra = _conv_graph(edge_index_or_graph, z.size(0), edge_weight, degree_on, "gcn_aggregate")
+    return _GCNAggregateFn.apply(z, bias, g, *extra)
 
 
 # ----------------------------------------------------------------------------- K8
@@ -681,6 +745,129 @@ def ebgcn_conv2_lin(h1: torch.Tensor, x: torch.Tensor, batch: torch.Tensor, root
                                  stream_handle()))
     if validate and int(status.item()) & 1:
         raise IndexError("rootindex / batch contains an index out of range")
+    return z2
+
+
+def _rows16(t: torch.Tensor) -> torch.Tensor:
+    """``t`` [n, c] as fp32 rows the float4 kernels read in place (unit column stride, a row stride
+    that is a multiple of 4, a 16-byte aligned base), else a contiguous fp32 copy."""
+    t = t.detach()
+    if t.dtype == torch.float32 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0:
+        return t
+    return t.to(torch.float32).contiguous()
+
+
+class _Conv2LinTrainFn(torch.autograd.Function):
+    """``bgcn_ebgcn_conv2_lin_train_fwd`` / ``_bwd``.  Gradients reach h1, W2, bn1's weight and bias.
+    ``meta``: eps and status in; batch_mean, batch_var (biased), num_valid, bn_g and bn_t out."""
+
+    @staticmethod
+    def forward(ctx, meta, h1, weight, gamma, beta, x, batch, rootindex):
+        dev = h1.device
+        hc, w2, ga, be = _rows16(h1), _f32c(weight), _f32c(gamma), _f32c(beta)
+        N, B, F = int(hc.size(0)), int(rootindex.numel()), int(x.size(1))
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        z2 = torch.empty(N, 64, **f32)
+        stats = torch.empty(4, 64 + F, **f32)    # batch mean, biased batch variance, the fold's g and t
+        a_x = torch.empty(B, F, **f32)
+        tree_count, nvalid = torch.empty(B, **i32), torch.empty(1, **i32)
+        a = _lib.Conv2LinTrainFwdArgs()
+        a.h1, a.ldh, a.x, a.ldx = hc.data_ptr(), hc.stride(0), x.data_ptr(), x.stride(0)
+        a.batch, a.rootindex = batch.data_ptr(), rootindex.data_ptr()
+        a.num_nodes, a.num_graphs, a.in_feats, a.hid = N, B, F, int(hc.size(1))
+        a.w2, a.gamma, a.beta, a.eps = w2.data_ptr(), ga.data_ptr(), be.data_ptr(), meta["eps"]
+        a.z2, a.ldz = z2.data_ptr(), 64
+        a.batch_mean, a.batch_var, a.bn_g, a.bn_t = (stats[k].data_ptr() for k in range(4))
+        a.a_x, a.tree_count, a.num_valid = a_x.data_ptr(), tree_count.data_ptr(), nvalid.data_ptr()
+        a.status = meta["status"].data_ptr()
+        L = _lib.lib()
+        ws = workspace(L.bgcn_ebgcn_conv2_lin_train_workspace_size(N, B, F), dev)
+        check(L.bgcn_ebgcn_conv2_lin_train_fwd(ctypes.addressof(a), ws.data_ptr(), ws.numel(), stream_handle()))
+        ctx.save_for_backward(hc, x, batch, rootindex, w2, stats, a_x, tree_count, nvalid)
+        ctx.eps = meta["eps"]
+        ctx.in_dtypes = tuple(t.dtype for t in (h1, weight, gamma, beta))
+        meta["batch_mean"], meta["batch_var"], meta["bn_g"], meta["bn_t"] = stats.unbind(0)
+        meta["num_valid"] = nvalid
+        return z2
+
+    @staticmethod
+    def backward(ctx, dz2):
+        hc, x, batch, rootindex, w2, stats, a_x, tree_count, nvalid = ctx.saved_tensors
+        dev = hc.device
+        N, B, F = int(hc.size(0)), int(rootindex.numel()), int(x.size(1))
+        dz2 = _rows16(dz2)
+        f32 = dict(dtype=torch.float32, device=dev)
+        dh1, dw2 = torch.empty(N, 64, **f32), torch.empty(64, 64 + F, **f32)
+        dgb = torch.empty(2, 64 + F, **f32)
+        a = _lib.Conv2LinTrainBwdArgs()
+        a.dz2, a.lddz, a.h1, a.ldh, a.x, a.ldx = dz2.data_ptr(), dz2.stride(0), hc.data_ptr(), hc.stride(0), \
+            x.data_ptr(), x.stride(0)
+        a.batch, a.rootindex = batch.data_ptr(), rootindex.data_ptr()
+        a.num_nodes, a.num_graphs, a.in_feats, a.hid = N, B, F, 64
+        a.w2, a.eps = w2.data_ptr(), ctx.eps
+        a.batch_mean, a.batch_var, a.bn_g, a.bn_t = (stats[k].data_ptr() for k in range(4))
+        a.a_x, a.tree_count, a.num_valid = a_x.data_ptr(), tree_count.data_ptr(), nvalid.data_ptr()
+        a.dh1, a.ldd, a.dw2, a.dgamma, a.dbeta = dh1.data_ptr(), 64, dw2.data_ptr(), dgb[0].data_ptr(), dgb[1].data_ptr()
+        L = _lib.lib()
+        ws = workspace(L.bgcn_ebgcn_conv2_lin_train_workspace_size(N, B, F), dev)
+        check(L.bgcn_ebgcn_conv2_lin_train_bwd(ctypes.addressof(a), ws.data_ptr(), ws.numel(), stream_handle()))
+        # (the passes share their intermediates: all four are always computed)
+        grads = tuple(g.to(dt) if need else None
+                      for g, dt, need in zip((dh1, dw2, dgb[0], dgb[1]), ctx.in_dtypes, ctx.needs_input_grad[1:5]))
+        return (None,) + grads + (None, None, None)
+
+
+def ebgcn_conv2_lin_train(h1: torch.Tensor, x: torch.Tensor, batch: torch.Tensor, rootindex: torch.Tensor,
+                          weight: torch.Tensor, bn1: torch.nn.Module,
+                          status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv2's lin of the EBGCN direction in TRAINING mode (``EBGCN.py:72-84``): ``relu(bn1(cat(h1,
+    x[root of the node's tree]))) W2^T`` [N, 64] with bn1 on batch statistics, as one autograd function
+    on ``bgcn_ebgcn_conv2_lin_train_fwd`` / ``_bwd``.  The [N, 64 + F] concat is never formed: the
+    root columns' statistics, product and gradients are taken over the B root rows weighted by tree
+    size; the largest arrays are [B, F] and [N, 64].
+
+    Gradients reach ``h1``, ``weight``, ``bn1.weight`` and ``bn1.bias``; ``x`` is data
+    (``x.requires_grad`` raises ``ValueError``).  bn1's running statistics and ``num_batches_tracked``
+    are updated as ``torch.nn.BatchNorm1d`` does in training (``momentum=None``: the cumulative
+    average; ``track_running_stats=False``: nothing to update).  A node whose tree id is outside
+    [0, B) or whose tree's rootindex is outside [0, N) is left out of the statistics, gets a zero row
+    and a zero gradient and sets ``status`` (int32 [1], optional) to 1; a batch with fewer than two
+    valid nodes gives zeros and blends nothing (decided on the device, no sync)."""
+    if bn1 is None or bn1.weight is None or bn1.bias is None:
+        raise ValueError("ebgcn_conv2_lin_train needs an affine BatchNorm")
+    _dev_check(h1, x, batch, rootindex, weight, bn1.weight)
+    if x.requires_grad:
+        raise ValueError("ebgcn_conv2_lin_train: x is data and gets no gradient (x.requires_grad is set)")
+    if h1.dim() != 2 or x.dim() != 2 or h1.size(1) != 64:
+        raise ValueError("ebgcn_conv2_lin_train: h1 must be [N, 64] and x [N, F]")
+    N, F, B = int(h1.size(0)), int(x.size(1)), int(rootindex.numel())
+    if x.size(0) != N or batch.numel() != N or weight.shape != (64, 64 + F) or bn1.weight.numel() != 64 + F:
+        raise ValueError("ebgcn_conv2_lin_train: shapes do not match (h1 [N, 64], x [N, F], batch [N], "
+                         "W2 [64, 64 + F], bn1 over 64 + F)")
+    if N == 0 or B == 0 or F == 0 or F % 4:
+        raise ValueError("ebgcn_conv2_lin_train needs N > 0, B > 0 and F a positive multiple of 4")
+    x = _rows16(x)
+    batch, rootindex = batch.to(torch.int64).contiguous(), rootindex.to(torch.int64).contiguous()
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=h1.device)
+    meta = {"eps": float(bn1.eps), "status": status}
+    z2 = _Conv2LinTrainFn.apply(meta, h1, weight, bn1.weight, bn1.bias, x, batch, rootindex)
+    if bn1.track_running_stats and bn1.running_mean is not None:
+        with torch.no_grad():
+            # fewer than two valid nodes: no statistics, nothing blended (decided on the device, no sync)
+            nv = meta["num_valid"]
+            some = nv >= 2
+            rm, rv = bn1.running_mean, bn1.running_var
+            if bn1.num_batches_tracked is not None:
+                bn1.num_batches_tracked += some.to(bn1.num_batches_tracked.dtype).view(())
+            if bn1.momentum is None:   # cumulative average over the batches tracked so far
+                f = some.to(rm.dtype) / bn1.num_batches_tracked.clamp(min=1).to(rm.dtype)
+            else:
+                f = some.to(rm.dtype) * float(bn1.momentum)
+            n = nv.to(rv.dtype)
+            unbiased = meta["batch_var"].to(rv.dtype) * (n / (n - 1).clamp(min=1))
+            rm.add_(f * (meta["batch_mean"].to(rm.dtype) - rm))
+            rv.add_(f * (unbiased - rv))
     return z2
 
 

@@ -853,6 +853,90 @@ int bgcn_edge_infer_train_bwd(const bgcn_edge_train_bwd_args* args, void* worksp
                               bgcn_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * EBGCN bn1 + relu + conv2's lin in TRAINING mode (model/Twitter/EBGCN.py:72-84) and the backward,
+ * without the dense [N, 64 + F] concat.  Additive entry points: BGCN_ABI_VERSION is unchanged.
+ *
+ * The concat row of node i is c_i = [h1_i | x[rootindex[batch_i]]]; n_b = nodes of tree b, N = the
+ * valid nodes.  Forward:
+ *   h columns: mean / biased variance over the N rows of h1
+ *   x columns: mean = (1/N) sum_b n_b x[r_b],  var = (1/N) sum_b n_b (x[r_b] - mean)^2
+ *   bn_g = gamma / sqrt(var + eps),  bn_t = beta - mean bn_g
+ *   z2_i = relu(g_h h1_i + t_h) W2[:, :64]^T + r[batch_i],  r[b] = a_x[b] W2[:, 64:]^T,
+ *   a_x[b] = relu(g_x x[r_b] + t_x)
+ * z2 has the bits of bgcn_ebgcn_conv2_lin called with the returned bn_g / bn_t (it is that code).
+ * batch_var is the BIASED variance; torch blends var N / (N - 1) into running_var (the caller
+ * does the blend, with *num_valid).  Backward, dR[b] = sum_{i in b} dz2_i, a_h = relu(y_h):
+ *   dW2[:, :64] = dz2^T a_h                dW2[:, 64:] = dR^T a_x      (B rows, not N)
+ *   dY_h = (dz2 W2[:, :64]) . [y_h > 0]    dY_x[b] = (dR[b] W2[:, 64:]) . [y_x[b] > 0]
+ *   dbeta = column sums of dY (N rows / B rows);  dgamma = those of dY . chat, chat = (c - mean) rstd
+ *   dh1_i = g_h . (dY_h,i - dbeta_h / N - chat_h,i . dgamma_h / N)        (x gets no gradient)
+ * The backward OVERWRITES dh1 [N, ldd >= 64], dw2 [64, 64 + F] (leading dimension 64 + F), dgamma
+ * and dbeta [64 + F].
+ *
+ * Nothing of size N x F is read or written; the largest arrays are [B, F] and [N, 64].
+ * Workspace (one size serves both calls): bgcn_ebgcn_conv2_lin's, the statistics' block partials
+ * ([ceil(N / 256)] and [ceil(B / 32)] triples per column), a_h and dz2 W2[:, :64] [N, 64] each,
+ * dR [B, 64], dR W2[:, 64:] [B, F], the backward's block partials and bgcn_gemm_tn's split
+ * partials; 0 = bad sizes.
+ * Deterministic: no float atomics; every float sum goes through block partials and one ordered
+ * pass, variances are of centred values (an ordered merge of per-block (n, mean, M2) triples).
+ * The batch vector need not be sorted.
+ *
+ * A node is invalid when its tree id is outside [0, B) or its tree's rootindex outside [0, N): it
+ * is never read through, is left out of N and of every statistic, gets a zero z2 row and a zero
+ * dh1 row, and sets bit 0 of *status (the forward does not zero *status).  A tree id without
+ * nodes has weight 0.  With *num_valid < 2 there are no batch statistics: every output of both
+ * calls is zero (decided on the device).
+ *
+ * BGCN_EINVAL before any HIP call: hid != 64 ("hidden size must be 64"), in_feats not a positive
+ * multiple of 4 ("in_feats"), N <= 0 or B <= 0, "batch too large", leading dimensions not
+ * multiples of 4 or too short, a negative eps, a "null pointer", pointers not "16-byte aligned",
+ * "workspace too small".
+ * -------------------------------------------------------------------------- */
+typedef struct bgcn_conv2_lin_train_fwd_args {
+  const float* h1; int64_t ldh;    /* conv1's output [N, ldh >= 64]                */
+  const float* x; int64_t ldx;     /* the features [N, ldx >= F], fp32             */
+  const int64_t* batch;            /* [N] node -> tree                             */
+  const int64_t* rootindex;        /* [B] tree -> root node                        */
+  int64_t num_nodes; int64_t num_graphs; int64_t in_feats;
+  int64_t hid;                     /* hid == 64                                    */
+  const float* w2;                 /* conv2.lin.weight [64, 64 + F]                */
+  const float* gamma; const float* beta;   /* bn1.weight, bn1.bias [64 + F]        */
+  float eps;                       /* bn1.eps                                      */
+  float* z2; int64_t ldz;          /* [N, ldz >= 64]                               */
+  float* batch_mean; float* batch_var;     /* [64 + F] each (biased variance)      */
+  float* bn_g; float* bn_t;        /* saved: [64 + F] each, the fold               */
+  float* a_x;                      /* saved: [B, F] the activated root table       */
+  int32_t* tree_count;             /* saved: [B] valid nodes per tree              */
+  int32_t* num_valid;              /* saved: [1] valid nodes                       */
+  int32_t* status;                 /* [1]                                          */
+} bgcn_conv2_lin_train_fwd_args;
+typedef struct bgcn_conv2_lin_train_bwd_args {
+  const float* dz2; int64_t lddz;  /* [N, lddz >= 64]                              */
+  const float* h1; int64_t ldh;
+  const float* x; int64_t ldx;
+  const int64_t* batch;
+  const int64_t* rootindex;
+  int64_t num_nodes; int64_t num_graphs; int64_t in_feats;
+  int64_t hid;
+  const float* w2;
+  float eps;
+  const float* batch_mean; const float* batch_var;
+  const float* bn_g; const float* bn_t;
+  const float* a_x;
+  const int32_t* tree_count;
+  const int32_t* num_valid;
+  float* dh1; int64_t ldd;         /* [N, ldd >= 64]                               */
+  float* dw2;                      /* [64, 64 + F]                                 */
+  float* dgamma; float* dbeta;     /* [64 + F] each                                */
+} bgcn_conv2_lin_train_bwd_args;
+size_t bgcn_ebgcn_conv2_lin_train_workspace_size(int64_t num_nodes, int64_t num_graphs, int64_t in_feats);
+int bgcn_ebgcn_conv2_lin_train_fwd(const bgcn_conv2_lin_train_fwd_args* args, void* workspace,
+                                   size_t workspace_bytes, bgcn_stream_t stream);
+int bgcn_ebgcn_conv2_lin_train_bwd(const bgcn_conv2_lin_train_bwd_args* args, void* workspace,
+                                   size_t workspace_bytes, bgcn_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * Optimiser step of the training loop: torch.optim.Adam with the reference's three
  * parameter groups (BiGCN_Twitter.py:146-153, step at :189) as ONE fused launch.
  * amsgrad = False; weight_decay is L2 added to the gradient (torch Adam semantics).
