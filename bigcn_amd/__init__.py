@@ -11,6 +11,9 @@ Drop-in symbols for the reference's hot path (cwkd/BiGCN):
   with batch-statistics BatchNorm, the Bayesian branch, the KL edge loss and their backward) and
   ``ebgcn_conv2_lin_train`` (batch-statistics bn1 + relu + conv2's lin and their backward without the
   dense [N, 64 + F] concat) followed by ``gcn_aggregate`` (the aggregation half of ``gcn_conv``)
+* ``EBGCNTrainStep`` - EBGCN's training-loop body (EBGCN.py:300-312) without a host sync: the training
+  forward, the loss / accuracy / skip decision in one launch, backward, and ``MultiAdam`` (one launch for
+  all 68 parameter tensors in the reference's five groups, ``ebgcn_adam``)
 * ``explain`` / ``segment_rank`` - the reference's analysis (explain_PHEME.py): per-stage node sums and
   per-tree rankings of a whole batch, for ``BiGCN`` / ``Net`` / ``EBGCN`` in eval mode
 * ``compare`` / ``tree_centrality`` / ``rank_similarity`` - the reference's comparison
@@ -34,12 +37,15 @@ from . import metrics
 from .metrics import EpochMetrics, class_metrics, confusion, evaluation4class, evaluationclass
 from .ops import (Graph, bigcn_encoder, build_graph, ebgcn_conv2_lin_train, edge_infer, edge_infer_train,
                   gcn_aggregate, gcn_conv, scatter_mean, spmm)
-from .optim import FusedAdam, bigcn_adam
+from .ops import drop_edges
+from .optim import FusedAdam, MultiAdam, bigcn_adam, ebgcn_adam
+from .ebgcn_step import EBGCNTrainStep
 from .train import FusedTrainStep
 
 __all__ = ["GCNConv", "scatter_mean", "TDrumorGCN", "BUrumorGCN", "BiGCN", "Net", "make_optimizer",
            "Graph", "build_graph", "gcn_conv", "spmm", "bigcn_encoder", "FusedAdam", "bigcn_adam",
            "FusedTrainStep", "EBGCN", "edge_infer", "edge_infer_train", "ebgcn_conv2_lin_train", "gcn_aggregate",
+           "MultiAdam", "ebgcn_adam", "EBGCNTrainStep", "drop_edges",
            "explain", "segment_rank",
            "compare", "tree_centrality", "rank_similarity",
            "metrics", "confusion", "class_metrics", "evaluation4class", "evaluationclass", "EpochMetrics"]

@@ -68,7 +68,27 @@ EXPORTED_SYMBOLS = (
     "bgcn_ebgcn_eval_workspace_size", "bgcn_ebgcn_eval_step", "bgcn_ebgcn_eval_saved",
     "bgcn_edge_infer_train_workspace_size", "bgcn_edge_infer_train_fwd", "bgcn_edge_infer_train_bwd",
     "bgcn_ebgcn_conv2_lin_train_workspace_size", "bgcn_ebgcn_conv2_lin_train_fwd", "bgcn_ebgcn_conv2_lin_train_bwd",
+    "bgcn_adam_multi_table_size", "bgcn_adam_multi_plan", "bgcn_adam_multi_step", "bgcn_ebgcn_train_loss",
 )
+
+BGCN_ADAM_MULTI_MAX_TENSORS = 128
+BGCN_ADAM_MULTI_MAX_GROUPS = 8
+BGCN_ADAM_MULTI_CHUNK = 1024   # elements per workgroup of bgcn_adam_multi_step
+
+
+class AdamMultiTensor(Structure):
+    """bgcn_adam_multi_tensor (include/bgcn.h): one entry of the many-tensor Adam's table."""
+    _fields_ = [("param", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("numel", c_int64),
+                ("first_block", c_int64), ("group", c_int32), ("reserved", c_int32)]
+
+
+class AdamMultiArgs(Structure):
+    """bgcn_adam_multi_args (include/bgcn.h)."""
+    _fields_ = [("table", c_void_p), ("count", c_int32), ("blocks", c_int64),
+                ("grad", c_void_p * BGCN_ADAM_MULTI_MAX_TENSORS), ("lr", c_float * BGCN_ADAM_MULTI_MAX_GROUPS),
+                ("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("weight_decay", c_float),
+                ("bias_correction1", c_float), ("bias_correction2_sqrt", c_float), ("grad_scale", c_float),
+                ("skip_flag", c_void_p), ("skip_count", c_void_p)]
 
 
 class SpmmPlan(Structure):
@@ -331,6 +351,12 @@ _SIGS = {
     "bgcn_ebgcn_conv2_lin_train_workspace_size": (c_size_t, [c_int64, c_int64, c_int64]),
     "bgcn_ebgcn_conv2_lin_train_fwd": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_ebgcn_conv2_lin_train_bwd": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "bgcn_adam_multi_table_size": (c_size_t, [c_int]),
+    "bgcn_adam_multi_plan": (c_int, [c_void_p, c_int, c_void_p, c_size_t, POINTER(c_int64)]),
+    "bgcn_adam_multi_step": (c_int, [c_void_p, c_void_p]),
+    "bgcn_ebgcn_train_loss": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_float, c_float,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

@@ -84,28 +84,34 @@ class _EdgeRumorGCN(torch.nn.Module):
             return edge_infer_train(x, edge_index, self, noise=noise, generator=generator, status=status)
         return None, edge_infer(x, edge_index, self, status=status)
 
-    def _train_encode(self, data, noise, generator, status):
+    def _train_encode(self, data, noise, generator, status, graph_status=None):
         """The training forward of one direction (``:61-93``) with autograd: ``(x [B, 128],
         edge_loss or None)``.  The ``[N, 64 + F]`` concat is never formed (a one-node batch, whose bn1
-        the reference skips, keeps the torch composition)."""
+        the reference skips, keeps the torch composition).  Nothing here reads ``status`` on the
+        host.  ``graph_status``: the word the convolutions' graph builds OR their own status
+        words into (``None``: they stay with the graphs, unread)."""
         x = data.x.float()
         ei = getattr(data, self.edge_key)
         batch, rootindex = data.batch, data.rootindex
         N = x.size(0)
-        h1 = gcn_conv(x, ei, self.conv1.lin.weight, self.conv1.bias, degree_on=self.conv1.degree_on)   # :64
+        h1 = gcn_conv(x, ei, self.conv1.lin.weight, self.conv1.bias, degree_on=self.conv1.degree_on,
+                      status=graph_status)                                     # :64
         edge_loss = edge_pred = None
         if bool(getattr(self.args, self.infer_flag)):                          # :67-70
             edge_loss, edge_pred = edge_infer_train(h1, ei, self, noise=noise, generator=generator, status=status)
-        root_of_node = rootindex[batch]
+        # a root outside [0, N) is flagged by conv2's lin; the torch gathers below read a clamped row
+        # (the step is invalid either way), never memory outside h1 / x
+        root_of_node = rootindex[batch].clamp(0, max(N - 1, 0))
         if N != 1:
             # :72-84 cat, bn1 on batch statistics, relu and conv2's lin without the concat, then conv2's
             # aggregation
             z2 = ebgcn_conv2_lin_train(h1, x, batch, rootindex, self.conv2.lin.weight, self.bn1, status=status)
-            h2 = gcn_aggregate(z2, ei, self.conv2.bias, edge_weight=edge_pred, degree_on=self.conv2.degree_on)
+            h2 = gcn_aggregate(z2, ei, self.conv2.bias, edge_weight=edge_pred, degree_on=self.conv2.degree_on,
+                               status=graph_status)
         else:                                                                  # :80-81, bn1 skipped
             cat = torch.relu(torch.cat((h1, x.index_select(0, root_of_node)), 1))
             h2 = gcn_conv(cat, ei, self.conv2.lin.weight, self.conv2.bias, edge_weight=edge_pred,
-                          degree_on=self.conv2.degree_on)                      # :84
+                          degree_on=self.conv2.degree_on, status=graph_status)  # :84
         # :65 x2 = copy.copy(x) is a copy outside the autograd graph: as in the reference, no
         # gradient reaches conv1 through the root rows of the readout (:86-90)
         h = torch.cat((torch.relu(h2), h1.detach().index_select(0, root_of_node)), 1)
@@ -203,16 +209,22 @@ class EBGCN(torch.nn.Module):
         Per direction it composes ``gcn_conv`` (conv1), :func:`bigcn_amd.ops.edge_infer_train` (fused),
         :func:`bigcn_amd.ops.ebgcn_conv2_lin_train` (fused: batch-statistics bn1, relu and conv2's lin
         without the dense ``[N, 64 + F]`` concat), :func:`bigcn_amd.ops.gcn_aggregate` with
-        ``edge_weight=edge_pred`` and ``scatter_mean``; conv1, the readout and the optimiser are
-        separate calls, a one-call EBGCN step is not built.  An index out of range raises ``IndexError`` at the end of
+        ``edge_weight=edge_pred`` and ``scatter_mean``; conv1 and the readout are separate calls
+        (:class:`bigcn_amd.EBGCNTrainStep` is the loop body around this forward, without its sync).  An index out of range raises ``IndexError`` at the end of
         the call (one host sync); the BatchNorms have by then been updated from the valid part of
         the batch (a direction without one valid edge leaves its per-edge norms untouched)."""
-        td_noise, bu_noise = (None, None) if noise is None else noise
         status = torch.zeros(1, dtype=torch.int32, device=data.x.device)
-        td_x, td_loss = self.TDrumorGCN._train_encode(data, td_noise, generator, status)
-        bu_x, bu_loss = self.BUrumorGCN._train_encode(data, bu_noise, generator, status)
-        out = self.fc(torch.cat((bu_x, td_x), 1))                              # :227-228, BU first
+        out = self._train_body(data, noise, generator, status)
         _raise_on(status)
+        return out
+
+    def _train_body(self, data, noise, generator, status, graph_status=None):
+        """:meth:`train_forward` without its host sync: flags go into ``status`` (and the graph builds'
+        into ``graph_status``, see ``_train_encode``), which is not read here."""
+        td_noise, bu_noise = (None, None) if noise is None else noise
+        td_x, td_loss = self.TDrumorGCN._train_encode(data, td_noise, generator, status, graph_status)
+        bu_x, bu_loss = self.BUrumorGCN._train_encode(data, bu_noise, generator, status, graph_status)
+        out = self.fc(torch.cat((bu_x, td_x), 1))                              # :227-228, BU first
         return torch.nn.functional.log_softmax(out, dim=1), td_loss, bu_loss   # :229-230
 
     # ---- the evaluation loop (EBGCN.py:328-354) as one native call per batch

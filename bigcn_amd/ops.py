@@ -442,23 +442,31 @@ def _conv_graph(g, num_nodes: int, edge_weight, degree_on: str, what: str):
 
 def gcn_conv(x: torch.Tensor, edge_index_or_graph, weight: torch.Tensor,
              bias: Optional[torch.Tensor] = None, edge_weight: Optional[torch.Tensor] = None,
-             degree_on: str = "col") -> torch.Tensor:
+             degree_on: str = "col", status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``status`` (int32 [1], optional): the graph's status word (bit 0: an edge index out of range) is
+    OR-ed into it on the device, for a caller that reads one word at the end of a step."""
     _dev_check(x, weight, bias, edge_weight)
     g, extra = _conv_graph(edge_index_or_graph, x.size(0), edge_weight, degree_on, "gcn_conv")
+    if status is not None:
+        status.bitwise_or_(g.status)
     return _GCNConvFn.apply(x, weight, bias, g, *extra)
 
 
 def gcn_aggregate(z: torch.Tensor, edge_index_or_graph, bias: Optional[torch.Tensor] = None,
-                  edge_weight: Optional[torch.Tensor] = None, degree_on: str = "col") -> torch.Tensor:
+                  edge_weight: Optional[torch.Tensor] = None, degree_on: str = "col",
+                  status: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The aggregation half of :func:`gcn_conv`: ``A_hat z + bias`` with ``A_hat = gcn_norm(edge_index,
     edge_weight)``, for a ``z = x W^T`` [N, O] computed elsewhere.  Gradients reach ``z``, ``bias`` and a
-    learned ``edge_weight``; given ``z`` from the same product, the result has ``gcn_conv``'s bits."""
+    learned ``edge_weight``; given ``z`` from the same product, the result has ``gcn_conv``'s bits.
+    ``status``: as in :func:`gcn_conv`."""
     _dev_check(z, bias, edge_weight)
     if z.dim() != 2:
         raise ValueError("z must be [N, O]")
     if bias is not None and bias.numel() != z.size(1):
         raise ValueError("bias must have O elements")
     g, extra = _conv_graph(edge_index_or_graph, z.size(0), edge_weight, degree_on, "gcn_aggregate")
+    if status is not None:
+        status.bitwise_or_(g.status)
     return _GCNAggregateFn.apply(z, bias, g, *extra)
 
 

@@ -177,6 +177,151 @@ class FusedAdam:
         raise KeyError("parameter not managed by this optimiser")
 
 
+MULTI_MAX_TENSORS = _lib.BGCN_ADAM_MULTI_MAX_TENSORS
+MULTI_MAX_GROUPS = _lib.BGCN_ADAM_MULTI_MAX_GROUPS
+
+
+class MultiAdam:
+    """:class:`FusedAdam`'s interface for up to 128 tensors in up to 8 parameter groups, one launch
+    per step (``bgcn_adam_multi_step``, ``csrc/bgcn_adam_multi.hip``); the update has
+    ``FusedAdam``'s bits.  ``param_groups``: list of dicts {"params": [...], "lr": float} (torch
+    layout).
+
+    The table of parameter / moment pointers, sizes and groups is planned on the host
+    (``bgcn_adam_multi_plan``) and uploaded once, and again only when a parameter's or a moment's
+    storage changes; the gradient pointers and the groups' learning rates travel in the kernel
+    arguments, so a step copies nothing to the device.  A parameter whose gradient is ``None``
+    is left alone (no weight decay either), as by ``torch.optim.Adam``."""
+
+    def __init__(self, param_groups: Sequence[dict], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0):
+        self.param_groups = []
+        for g in param_groups:
+            self.param_groups.append({"params": [p for p in g["params"]], "lr": g.get("lr", lr)})
+        self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
+        self.step_count = 0
+        self.state = {}
+        self._cache = None
+        self._keep = []
+        self._check_limits()
+        for p in self.params():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError("MultiAdam: contiguous fp32 parameters only")
+            self.state[p] = (torch.zeros_like(p), torch.zeros_like(p))
+
+    def _check_limits(self) -> None:
+        if len(self.param_groups) > MULTI_MAX_GROUPS:
+            raise ValueError(f"MultiAdam handles at most {MULTI_MAX_GROUPS} parameter groups")
+        if sum(len(g["params"]) for g in self.param_groups) > MULTI_MAX_TENSORS:
+            raise ValueError(f"MultiAdam handles at most {MULTI_MAX_TENSORS} tensors")
+
+    def params(self) -> List[torch.nn.Parameter]:
+        return [p for g in self.param_groups for p in g["params"]]
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        for p in self.params():
+            if set_to_none:
+                p.grad = None
+            elif p.grad is not None:
+                p.grad.zero_()
+
+    def _table(self, ps):
+        """``(key, args, device table)``, rebuilt when a parameter, a moment or the grouping changed."""
+        for p in ps:
+            if p not in self.state:   # a parameter added to param_groups after construction
+                self.state[p] = (torch.zeros_like(p), torch.zeros_like(p))
+        key = (tuple((p.data_ptr(), p.numel(), self.state[p][0].data_ptr(), self.state[p][1].data_ptr())
+                     for p in ps),
+               tuple(len(g["params"]) for g in self.param_groups))
+        if self._cache is not None and self._cache[0] == key:
+            return self._cache
+        self._check_limits()
+        n = len(ps)
+        L = _lib.load_library()
+        nbytes = int(L.bgcn_adam_multi_table_size(n))
+        entries = (_lib.AdamMultiTensor * n)()
+        k = 0
+        for gi, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                if not p.is_contiguous() or p.dtype != torch.float32:
+                    raise ValueError("MultiAdam: contiguous fp32 parameters only")
+                m, v = self.state[p]
+                e = entries[k]
+                e.param, e.exp_avg, e.exp_avg_sq = ptr(p), ptr(m), ptr(v)
+                e.numel, e.group = p.numel(), gi
+                k += 1
+        host = torch.empty(nbytes, dtype=torch.uint8)
+        blocks = ctypes.c_int64()
+        check(L.bgcn_adam_multi_plan(ctypes.addressof(entries), n, host.data_ptr(), nbytes, ctypes.byref(blocks)))
+        table = host.to(ps[0].device)   # the one upload
+        a = _lib.AdamMultiArgs()
+        a.table, a.count, a.blocks = table.data_ptr(), n, blocks.value
+        self._cache = (key, a, table)
+        return self._cache
+
+    def step(self, grads: Optional[Sequence[Optional[torch.Tensor]]] = None, grad_scale: float = 1.0,
+             skip_flag: Optional[torch.Tensor] = None, skip_count: Optional[torch.Tensor] = None) -> None:
+        """``grads`` overrides ``p.grad`` (one entry per parameter in ``params()`` order, ``None``
+        allowed); ``skip_flag`` / ``skip_count`` as in :meth:`FusedAdam.prepare`.  Learning rates
+        are read from ``param_groups`` on every call."""
+        ps = self.params()
+        if not ps:
+            self.step_count += 1
+            return
+        gs = list(grads) if grads is not None else [p.grad for p in ps]
+        if len(gs) != len(ps):
+            raise ValueError("grads must have one entry per parameter")
+        _, a, _ = self._table(ps)
+        t = self.step_count + 1
+        b1, b2 = self.betas
+        keep = []   # non-contiguous gradients: contiguous copies, alive through the launch
+        grad = a.grad
+        for k, (p, gr) in enumerate(zip(ps, gs)):
+            if gr is None:
+                grad[k] = None
+                continue
+            if gr.dtype != torch.float32 or gr.numel() != p.numel():
+                raise ValueError("MultiAdam: a gradient must be fp32 and of its parameter's size")
+            if not gr.is_contiguous():
+                gr = gr.contiguous()
+                keep.append(gr)
+            grad[k] = gr.data_ptr()
+        for gi, g in enumerate(self.param_groups):
+            a.lr[gi] = float(g["lr"])
+        if skip_flag is not None and (skip_flag.dtype != torch.float32 or skip_flag.numel() != 1
+                                      or skip_flag.device != ps[0].device):
+            raise ValueError("skip_flag must be a one-element fp32 tensor on the parameters' device")
+        if skip_count is not None and (skip_count.dtype != torch.int32 or skip_count.numel() != 1):
+            raise ValueError("skip_count must be a one-element int32 tensor")
+        a.skip_flag, a.skip_count = ptr(skip_flag), ptr(skip_count)
+        a.beta1, a.beta2, a.eps, a.weight_decay = b1, b2, self.eps, self.weight_decay
+        a.bias_correction1 = 1.0 - b1 ** t
+        a.bias_correction2_sqrt = math.sqrt(1.0 - b2 ** t)
+        a.grad_scale = grad_scale
+        self._keep = keep
+        self.step_count += 1
+        check(_lib.lib().bgcn_adam_multi_step(ctypes.addressof(a), stream_handle()))
+
+
+def ebgcn_adam(model, args) -> MultiAdam:
+    """The reference's EBGCN optimiser (``EBGCN.py:249-260``) on :class:`MultiAdam`: five groups in
+    the reference's order - base (``args.lr``), BU conv1 and BU conv2 (``args.lr /
+    args.lr_scale_bu``), TD conv1 and TD conv2 (``args.lr / args.lr_scale_td``) - with
+    ``weight_decay = args.l2`` on all of them."""
+    td, bu = model.TDrumorGCN, model.BUrumorGCN
+    convs = (bu.conv1, bu.conv2, td.conv1, td.conv2)
+    ids = {id(p) for c in convs for p in c.parameters()}
+    lr = float(args.lr)
+    lr_bu, lr_td = lr / args.lr_scale_bu, lr / args.lr_scale_td
+    return MultiAdam([
+        {"params": [p for p in model.parameters() if id(p) not in ids]},
+        {"params": list(bu.conv1.parameters()), "lr": lr_bu},
+        {"params": list(bu.conv2.parameters()), "lr": lr_bu},
+        {"params": list(td.conv1.parameters()), "lr": lr_td},
+        {"params": list(td.conv2.parameters()), "lr": lr_td},
+    ], lr=lr, weight_decay=float(args.l2))
+
+
 def bigcn_adam(model, lr: float = 5e-4, weight_decay: float = 1e-4) -> FusedAdam:
     """The reference's optimiser (``BiGCN_Twitter.py:146-153``) on FusedAdam."""
     bu_ids = {id(p) for p in model.BUrumorGCN.conv1.parameters()}

@@ -977,6 +977,77 @@ typedef struct bgcn_adam_args {
 #define BGCN_IMAGE_BU_W2 4
 int bgcn_adam_step(const bgcn_adam_args* args, bgcn_stream_t stream);
 
+/* --------------------------------------------------------------------------
+ * The same update for MANY tensors in ONE launch: up to BGCN_ADAM_MULTI_MAX_TENSORS tensors in
+ * up to BGCN_ADAM_MULTI_MAX_GROUPS learning-rate groups (an EBGCN has 68 parameter tensors in five
+ * groups, EBGCN.py:249-260).  Additive entry points: BGCN_ABI_VERSION is unchanged.
+ *
+ * What is fixed between steps lives in a TABLE in device memory, one bgcn_adam_multi_tensor per
+ * tensor: param, exp_avg, exp_avg_sq, numel, the group and first_block, the tensor's first
+ * workgroup (a workgroup updates one chunk of BGCN_ADAM_MULTI_CHUNK elements of one tensor;
+ * first_block[k] = sum over j < k of ceil(numel[j] / BGCN_ADAM_MULTI_CHUNK)).
+ * bgcn_adam_multi_plan fills a HOST image of it from the caller's entries (param, exp_avg,
+ * exp_avg_sq, numel, group; first_block is written by the plan) and returns the launch's workgroup
+ * count; the caller copies the image to the device once, and again only when a tensor's storage
+ * changes.  What changes every step travels in the kernel arguments (no per-step host-to-device
+ * copy): the gradient pointers, the groups' learning rates, the step's constants, skip_flag and
+ * skip_count.  grad[k] == NULL is torch.optim.Adam's `grad is None`: tensor k's parameter and both
+ * moments are not touched (no weight decay either).  A workgroup finds its tensor by a binary
+ * search over first_block.  The arithmetic is bgcn_adam_step's (the same bits); skip_flag and
+ * skip_count behave as there.
+ *
+ * BGCN_EINVAL, decided on the host before any launch: count outside [1, 128], a null table, a
+ * table buffer smaller than bgcn_adam_multi_table_size(count), a group outside [0, 8), numel < 0,
+ * a null param / exp_avg / exp_avg_sq where numel > 0, more than 2^31 - 1 workgroups (plan);
+ * count outside [1, 128], a null table, blocks < 0 (step).
+ * -------------------------------------------------------------------------- */
+#define BGCN_ADAM_MULTI_MAX_TENSORS 128
+#define BGCN_ADAM_MULTI_MAX_GROUPS 8
+#define BGCN_ADAM_MULTI_CHUNK 1024
+typedef struct bgcn_adam_multi_tensor {
+  float* param; float* exp_avg; float* exp_avg_sq;
+  int64_t numel;
+  int64_t first_block;           /* written by bgcn_adam_multi_plan          */
+  int32_t group;                 /* index into bgcn_adam_multi_args.lr       */
+  int32_t reserved;
+} bgcn_adam_multi_tensor;
+typedef struct bgcn_adam_multi_args {
+  const bgcn_adam_multi_tensor* table;   /* device memory, [count]          */
+  int32_t count;
+  int64_t blocks;                /* bgcn_adam_multi_plan's total             */
+  const float* grad[BGCN_ADAM_MULTI_MAX_TENSORS];   /* NULL: no gradient this step */
+  float lr[BGCN_ADAM_MULTI_MAX_GROUPS];
+  float beta1, beta2, eps, weight_decay;
+  float bias_correction1, bias_correction2_sqrt, grad_scale;
+  const float* skip_flag;        /* [1] or NULL                              */
+  int32_t* skip_count;           /* [1] or NULL                              */
+} bgcn_adam_multi_args;
+size_t bgcn_adam_multi_table_size(int count);   /* 0 for a count outside [1, 128] */
+int bgcn_adam_multi_plan(const bgcn_adam_multi_tensor* tensors, int count, void* table_host,
+                         size_t table_bytes, int64_t* blocks);
+int bgcn_adam_multi_step(const bgcn_adam_multi_args* args, bgcn_stream_t stream);
+
+/* --------------------------------------------------------------------------
+ * The loss of EBGCN's training loop (EBGCN.py:301-306), its accuracy (:311-312), the gradient
+ * the backward starts from and the step's skip decision, in one single-workgroup launch:
+ *   loss    = -mean_i logp[i][y_i] + edge_loss_td * *td_loss + edge_loss_bu * *bu_loss
+ *             (td_loss / bu_loss NULL: that direction's edge inference is off, no term)
+ *   correct = #{i : argmax_c logp[i][c] == y_i}, pred[i] (optional) that argmax, the first index
+ *             of the row maximum as torch.max gives it
+ *   dlogp   = [B, C]: -1 / B at (i, y_i), 0 elsewhere
+ * A label outside [0, C) sets bit 1 (value 2) of *status, as bgcn_ebgcn_eval_step does; that tree
+ * adds nothing to the loss (the mean still divides by B) and its dlogp row is zero.  *skip_flag =
+ * 1 when *status is non-zero after that (set by the step's forward or here), else 0: the
+ * optimiser's skip_flag.  *status_seen (optional) |= *status.  The sums are deterministic: tree i
+ * goes to lane i % 256 in order, a fixed butterfly per wave, the four waves in order.
+ * BGCN_EINVAL: num_graphs < 1, num_classes outside [1, 16], a null logp / y / loss / correct /
+ * dlogp / status / skip_flag.
+ * -------------------------------------------------------------------------- */
+int bgcn_ebgcn_train_loss(const float* logp, const int64_t* y, int64_t num_graphs, int32_t num_classes,
+                          const float* td_loss, const float* bu_loss, float edge_loss_td, float edge_loss_bu,
+                          float* loss, int32_t* correct, int64_t* pred, float* dlogp, int32_t* status,
+                          float* skip_flag, int32_t* status_seen, bgcn_stream_t stream);
+
 /* Materialise the in-kernel dropout keep bits (for tests / debugging):
  * words[dir][n][w] for dir in {0 (TD), 1 (BU)}. */
 int bgcn_keep_words(uint64_t seed, int64_t num_nodes, int32_t num_words, uint32_t* words,
