@@ -410,6 +410,19 @@ def check(rc: int) -> None:
         raise BGCNError(f"libbgcn error {rc}: {msg}")
 
 
+def raise_on_status(word: int, bits: int = 1 | 2 | 8, index_also: str = "", suffix: str = "") -> None:
+    """Raise what a status word of the library reports, looking at ``bits`` only: 8 an internal
+    hand-off timed out, 1 an index out of range (``index_also`` names what else sets it in the
+    caller's kernels), 2 a label out of range.  ``suffix`` ends either ``IndexError``'s message."""
+    word &= bits
+    if word & 8:
+        raise RuntimeError("libbgcn: an internal cross-workgroup hand-off timed out")
+    if word & 1:
+        raise IndexError("the batch holds an edge, root or tree index out of range" + index_also + suffix)
+    if word & 2:
+        raise IndexError("the batch holds a label outside [0, num_class)" + suffix)
+
+
 def stream_handle(device=None) -> int:
     """hipStream_t of the current torch stream (of `device`, default the current device).
     The per-call form reads torch's raw current stream (~0.1 us; the Stream object path

@@ -6,8 +6,8 @@
 // group, first workgroup - lives in a table in device memory that the caller uploads once, and
 // what changes every step - the gradient pointers autograd hands out afresh, the groups' learning
 // rates, the bias corrections, the skip flag - travels in the kernel arguments (about 1.1 KB), so
-// a step makes no host-to-device copy.  The arithmetic is adam_elem with k_adam's constants: the
-// same bits as bgcn_adam_step.
+// a step makes no host-to-device copy.  The update is bgcn_internal.h's adam_chunk, the one
+// k_adam's tensors without a weight image take.
 #include "bgcn_common.h"
 #include "bgcn_internal.h"
 
@@ -35,28 +35,7 @@ __global__ __launch_bounds__(256) void k_adam_multi(bgcn_adam_multi_args a) {
   const bgcn_adam_multi_tensor T = a.table[lo];
   const AdamConst c{a.beta1, a.beta2, a.weight_decay, a.eps, a.lr[T.group] / a.bias_correction1,
                     1.0f / a.bias_correction2_sqrt, a.grad_scale};
-  const int64_t e0 = (b - T.first_block) * kChunk + threadIdx.x * 4;
-  const bool vec = ((reinterpret_cast<uintptr_t>(T.param) | reinterpret_cast<uintptr_t>(grad) |
-                     reinterpret_cast<uintptr_t>(T.exp_avg) | reinterpret_cast<uintptr_t>(T.exp_avg_sq)) & 15u) == 0;
-  if (vec && e0 + 4 <= T.numel) {
-    float4 p = ld4(T.param + e0), g = ld4(grad + e0);
-    float4 m = ld4(T.exp_avg + e0), v = ld4(T.exp_avg_sq + e0);
-    adam_elem(p.x, g.x, m.x, v.x, c);
-    adam_elem(p.y, g.y, m.y, v.y, c);
-    adam_elem(p.z, g.z, m.z, v.z, c);
-    adam_elem(p.w, g.w, m.w, v.w, c);
-    st4(T.param + e0, p);
-    st4(T.exp_avg + e0, m);
-    st4(T.exp_avg_sq + e0, v);
-    return;
-  }
-  for (int64_t e = e0; e < e0 + 4 && e < T.numel; ++e) {
-    float p = T.param[e], m = T.exp_avg[e], v = T.exp_avg_sq[e];
-    adam_elem(p, grad[e], m, v, c);
-    T.param[e] = p;
-    T.exp_avg[e] = m;
-    T.exp_avg_sq[e] = v;
-  }
+  adam_chunk(T.param, grad, T.exp_avg, T.exp_avg_sq, T.numel, (b - T.first_block) * kChunk + threadIdx.x * 4, c);
 }
 
 bool count_ok(int count) { return count >= 1 && count <= BGCN_ADAM_MULTI_MAX_TENSORS; }

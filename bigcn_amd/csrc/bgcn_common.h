@@ -233,6 +233,22 @@ __device__ __forceinline__ float4 f4mul(float4 a, float4 b) {
 __device__ __forceinline__ float4 f4relu(float4 a) {
   return make_float4(fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(a.z, 0.f), fmaxf(a.w, 0.f));
 }
+__device__ __forceinline__ float4 f4affine(float4 g, float4 v, float4 t) {   // g v + t
+  return make_float4(fmaf(g.x, v.x, t.x), fmaf(g.y, v.y, t.y), fmaf(g.z, v.z, t.z), fmaf(g.w, v.w, t.w));
+}
+// BatchNorm1d with known statistics as one multiply-add y = g x + t (f4affine):
+// g = gamma / sqrt(var + eps), t = beta - mean g
+__device__ __forceinline__ void bn_fold(float gamma, float beta, float mean, float var, float eps, float& g,
+                                        float& t) {
+  const float gg = gamma / sqrtf(var + eps);
+  g = gg;
+  t = beta - mean * gg;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 
 inline unsigned grid_for(int64_t n, int block) { return unsigned((n + block - 1) / block); }
 

@@ -14,12 +14,11 @@
 // here, not corrected.
 //
 // Y is a 64 x 64 x 64 product per edge (524,288 FLOP, ~16 GFLOP per direction at the reference
-// batch).  It runs on the fp32 MFMA (exact fp32 products): Wc is the A operand, held in 64
-// registers per lane for the whole block; D is the B operand, made in registers from the two
-// 256-byte rows (one subtract + abs per element) and never stored; the epilogue (affine, leaky,
-// the w_out sum over o, the fc1 sum over l) runs on the accumulators.  One wave per edge, a
-// workgroup takes kEdgeTile edges; no atomics on floats, no scratch: an edge's bits depend on
-// nothing but its own rows.
+// batch).  It runs on the fp32 MFMA; the product and the epilogue on its accumulators (affine,
+// leaky, the w_out sum over o) are bgcn_edge_tile.h's, shared with the training kernels of
+// bgcn_ebgcn_train.hip; the fc1 sum over l follows here.  One wave per edge, a workgroup takes
+// kEdgeTile edges; no atomics on floats, no scratch: an edge's bits depend on nothing but its
+// own rows.
 //
 // bgcn_ebgcn_conv2_lin - conv2's lin (EBGCN.py:72-84) in eval mode:
 //   z2[i] = relu(g_h . h1[i] + t_h) W2[:, :64]^T + r[batch[i]],
@@ -28,16 +27,14 @@
 // one-node batch, :80).  The root block of the concat is the same row for every node of a
 // tree, so its F-wide product is done once per tree (bgcn_gemm_xwt on a [B, F] table), not
 // per node.  No dropout: the reference's EBGCN forward applies none.
+#include "bgcn_edge_tile.h"
 #include "bgcn_internal.h"
 
 namespace bgcn {
 namespace {
 
-constexpr int kH = 64;            // hidden size (the fork's only configuration)
 constexpr int kEdgeTile = BGCN_EDGE_INFER_TILE;   // edges per workgroup: 4 waves x 8 edges
 static_assert(kEdgeTile % 4 == 0, "one wave per edge, four waves per workgroup");
-constexpr int kMaxEdgeNum = 8;    // latent relation types (edge_num, default 2)
-constexpr int kWLd = kH + 1;      // LDS row stride of the Wc staging tile (conflict-free column reads)
 
 __global__ __launch_bounds__(256, 2) void k_edge_infer(
     const float* __restrict__ h, int64_t ldh, int64_t N, const int64_t* __restrict__ ei, int64_t E,
@@ -50,7 +47,7 @@ __global__ __launch_bounds__(256, 2) void k_edge_infer(
   __shared__ __attribute__((aligned(16))) float sO[kH];
   __shared__ float sF[kMaxEdgeNum * kH];
   const int tid = threadIdx.x;
-  for (int i = tid; i < kH * kH; i += 256) sW[(i >> 6) * kWLd + (i & 63)] = Wc[i];
+  stage_w(Wc, sW);
   if (tid < kH) {
     sG[tid] = g[tid];
     sT[tid] = t[tid];
@@ -59,12 +56,8 @@ __global__ __launch_bounds__(256, 2) void k_edge_infer(
   for (int i = tid; i < K * kH; i += 256) sF[i] = fc1[i];
   __syncthreads();
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), r32 = lane & 31, hh = lane >> 5;
-  // A operand of the f32 MFMA: lane (r32, hh) holds A[i = r32][k = hh] of each k-step
   float wa[2][32];
-#pragma unroll
-  for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-    for (int s = 0; s < 32; ++s) wa[tt][s] = sW[(32 * tt + r32) * kWLd + 2 * s + hh];
+  load_wa(sW, r32, hh, wa);
   const float bo = *bout;
   const float invK = 1.0f / float(K);
 
@@ -72,61 +65,20 @@ __global__ __launch_bounds__(256, 2) void k_edge_infer(
   for (int i = 0; i < kEdgeTile / 4; ++i) {
     const int64_t e = e0 + 4 * i;
     if (e >= E) break;
-    // wave-uniform edge ends (every lane reads the same two words)
-    const int64_t row = ei[e], col = ei[E + e];
-    if (row < 0 || row >= N || col < 0 || col >= N) {   // never a wild read
+    int64_t ia, ib;
+    if (!edge_ends(ei, E, N, e, ia, ib)) {
       if (lane == 0) {
         atomicOr(status, 1);
         pred[e] = 0.f;
       }
       continue;
     }
-    const int64_t ia = row == 0 ? N - 1 : row - 1;   // x[row - 1]: 0 wraps to the last node
-    const int64_t ib = col == 0 ? N - 1 : col - 1;
     const float av = h[ia * ldh + lane];
     const float b0 = h[ib * ldh + r32], b1 = h[ib * ldh + 32 + r32];
     f32x16 acc[2][2];
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[tt][u][r] = 0.f;
-    // B operand: lane (r32, hh) holds B[k = hh][j = r32] = D[c = 2s + hh][l = 32u + r32]
-#pragma unroll
-    for (int s = 0; s < 32; ++s) {
-      const float a = __shfl(av, 2 * s + hh);
-      const float d0 = fabsf(a - b0), d1 = fabsf(a - b1);
-      acc[0][0] = mfma32x32x2(wa[0][s], d0, acc[0][0]);
-      acc[0][1] = mfma32x32x2(wa[0][s], d1, acc[0][1]);
-      acc[1][0] = mfma32x32x2(wa[1][s], d0, acc[1][0]);
-      acc[1][1] = mfma32x32x2(wa[1][s], d1, acc[1][1]);
-    }
-    // acc[tt][u][r] = Y[o = 32tt + 8(r >> 2) + 4hh + (r & 3)][l = 32u + r32]
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int o0 = 32 * tt + 8 * q + 4 * hh;
-        const float4 G = *reinterpret_cast<const float4*>(&sG[o0]);
-        const float4 T = *reinterpret_cast<const float4*>(&sT[o0]);
-        const float4 O = *reinterpret_cast<const float4*>(&sO[o0]);
-        const float gv[4] = {G.x, G.y, G.z, G.w}, tv[4] = {T.x, T.y, T.z, T.w}, ov[4] = {O.x, O.y, O.z, O.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float z0 = fmaf(gv[j], acc[tt][0][4 * q + j], tv[j]);
-          float z1 = fmaf(gv[j], acc[tt][1][4 * q + j], tv[j]);
-          z0 = fmaxf(z0, 0.01f * z0);   // LeakyReLU(0.01): the slope is below 1
-          z1 = fmaxf(z1, 0.01f * z1);
-          s0 = fmaf(ov[j], z0, s0);
-          s1 = fmaf(ov[j], z1, s1);
-        }
-      }
-    s0 += __shfl_xor(s0, 32);   // the other half-wave holds the other rows o of the same l
-    s1 += __shfl_xor(s1, 32);
-    s0 += bo;
-    s1 += bo;
+    y_tile(wa, av, b0, b1, hh, acc);
+    const float2 sv = edge_out_sums(acc, sG, sT, sO, hh);
+    const float s0 = sv.x + bo, s1 = sv.y + bo;
     float sum = 0.f;
     for (int k = 0; k < K; ++k) {   // K is uniform: the shuffles stay convergent
       float p = fmaf(sF[k * kH + r32], s0, sF[k * kH + 32 + r32] * s1);
@@ -138,16 +90,13 @@ __global__ __launch_bounds__(256, 2) void k_edge_infer(
   }
 }
 
-// eval-mode BatchNorm1d as one multiply-add: g = gamma / sqrt(running_var + eps),
-// t = beta - running_mean g
+// eval-mode BatchNorm1d as one multiply-add: bn_fold of the running statistics
 __global__ __launch_bounds__(256) void k_bn_fold(const float* __restrict__ gamma, const float* __restrict__ beta,
                                                  const float* __restrict__ mean, const float* __restrict__ var,
                                                  float eps, int64_t C, float* __restrict__ g, float* __restrict__ t) {
   const int64_t c = int64_t(blockIdx.x) * 256 + threadIdx.x;
   if (c >= C) return;
-  const float gg = gamma[c] / sqrtf(var[c] + eps);
-  g[c] = gg;
-  t[c] = beta[c] - mean[c] * gg;
+  bn_fold(gamma[c], beta[c], mean[c], var[c], eps, g[c], t[c]);
 }
 
 // out[i][4q ..] = relu(g . in[src(i)][4q ..] + t), src(i) = gather[i] (or i); C4 = C / 4
@@ -164,10 +113,7 @@ __global__ __launch_bounds__(256) void k_affine_relu_rows(const float* __restric
   float4 v = f4zero();
   if (src >= 0 && src < src_rows) {
     v = ld4(in + src * ld_in + 4 * q);
-    if (g) {
-      const float4 gg = ld4(g + 4 * q), tt = ld4(t + 4 * q);
-      v = make_float4(fmaf(gg.x, v.x, tt.x), fmaf(gg.y, v.y, tt.y), fmaf(gg.z, v.z, tt.z), fmaf(gg.w, v.w, tt.w));
-    }
+    if (g) v = f4affine(ld4(g + 4 * q), v, ld4(t + 4 * q));
     v = f4relu(v);
   } else if (q == 0) {
     atomicOr(status, 1);
@@ -191,8 +137,6 @@ __global__ __launch_bounds__(256) void k_add_tree_rows(float* __restrict__ z, in
   float* p = z + i * ldz + 4 * q;
   st4(p, f4add(ld4(p), ld4(r + b * kH + 4 * q)));
 }
-
-bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 struct Conv2LinWs {
   float* root;   // [B, F]  relu(bn1(x[rootindex]))

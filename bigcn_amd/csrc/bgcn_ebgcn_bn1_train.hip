@@ -50,9 +50,6 @@ __device__ __forceinline__ float4 f4sub(float4 a, float4 b) {
 __device__ __forceinline__ float4 f4scale(float a, float4 x) { return make_float4(a * x.x, a * x.y, a * x.z, a * x.w); }
 // a true division: a column of equal values keeps its value as its mean (n v / n)
 __device__ __forceinline__ float4 f4div(float4 x, float a) { return make_float4(x.x / a, x.y / a, x.z / a, x.w / a); }
-__device__ __forceinline__ float4 f4affine(float4 g, float4 v, float4 t) {   // k_affine_relu_rows' expression
-  return make_float4(fmaf(g.x, v.x, t.x), fmaf(g.y, v.y, t.y), fmaf(g.z, v.z, t.z), fmaf(g.w, v.w, t.w));
-}
 __device__ __forceinline__ float4 f4rstd(float4 var, float eps) {
   return make_float4(1.0f / sqrtf(var.x + eps), 1.0f / sqrtf(var.y + eps), 1.0f / sqrtf(var.z + eps),
                      1.0f / sqrtf(var.w + eps));
@@ -218,7 +215,7 @@ __global__ __launch_bounds__(256) void k_stat_x(const float* __restrict__ x, int
 }
 
 // One thread per column of the concat: the ordered merge of the partial (n, mean, M2) triples, then
-// the fold (k_bn_fold's expressions).  Fewer than two valid nodes: no statistics, everything 0.
+// the fold (bn_fold, as in eval mode).  Fewer than two valid nodes: no statistics, everything 0.
 __global__ __launch_bounds__(256) void k_stats_fold(const int32_t* __restrict__ hn, const float* __restrict__ hmean,
                                                     const float* __restrict__ hm2, int Ph,
                                                     const int32_t* __restrict__ xn, const float* __restrict__ xmean,
@@ -253,8 +250,7 @@ __global__ __launch_bounds__(256) void k_stats_fold(const int32_t* __restrict__ 
   }
   float var = n > 0.f ? m2 / n : 0.f, gg = 0.f, tt = 0.f;
   if (*num_valid >= 2) {
-    gg = gamma[c] / sqrtf(var + eps);
-    tt = beta[c] - mean * gg;
+    bn_fold(gamma[c], beta[c], mean, var, eps, gg, tt);
   } else {
     mean = 0.f;
     var = 0.f;
@@ -265,7 +261,7 @@ __global__ __launch_bounds__(256) void k_stats_fold(const int32_t* __restrict__ 
   t[c] = tt;
 }
 
-// a_x[b] = relu(g_x x[r_b] + t_x) (k_affine_relu_rows' expression: the forward's own root table has
+// a_x[b] = relu(g_x x[r_b] + t_x) (f4affine, as k_affine_relu_rows: the forward's own root table has
 // these bits); zeros for a tree without valid nodes
 __global__ __launch_bounds__(256) void k_root_act(const float* __restrict__ x, int64_t ldx,
                                                   const int64_t* __restrict__ rootindex,
@@ -458,8 +454,6 @@ __global__ __launch_bounds__(256) void k_dh1(const float* __restrict__ h1, int64
   }
   st4(dh1 + i * ldd + 4 * q, out);
 }
-
-bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 struct Bn1TrainWs {
   void* conv2;        // conv2_lin_impl's workspace

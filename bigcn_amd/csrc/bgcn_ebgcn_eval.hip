@@ -53,9 +53,7 @@ __global__ __launch_bounds__(256) void k_eval_fold(FoldArgs a) {
   const int64_t c = int64_t(blockIdx.x) * 256 + threadIdx.x;
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *a.status = 0;
   if (c >= j.C) return;
-  const float gg = j.gamma[c] / sqrtf(j.var[c] + j.eps);   // k_bn_fold's expressions
-  j.g[c] = gg;
-  j.t[c] = j.beta[c] - j.mean[c] * gg;
+  bn_fold(j.gamma[c], j.beta[c], j.mean[c], j.var[c], j.eps, j.g[c], j.t[c]);
 }
 
 // ---- edge slots.  slot[e] = the entry of edge e in the by-target CSR (as fill_nodes / rank_norm
@@ -349,8 +347,6 @@ bool dir_complete(const bgcn_ebgcn_dir& d) {
          d.bn1_var && d.sim_conv_w && d.sim_norm_weight && d.sim_norm_bias && d.sim_norm_mean && d.sim_norm_var &&
          d.sim_out_w && d.sim_out_b && d.fc1_w;
 }
-
-bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

@@ -3,8 +3,9 @@
 // the backward through the sim network, fc1 and h.  include/bgcn.h states the mathematics.
 //
 // Per edge and network Y = Wc D is a 64 x 64 x 64 product on the fp32 MFMA, with D = |a - b^T|
-// made in registers from the two 256-byte rows (as k_edge_infer of bgcn_ebgcn.hip does).  Nothing
-// [E, 64, 64] is ever stored: every pass that needs Y computes it again.
+// made in registers from the two 256-byte rows: bgcn_edge_tile.h has the product and the networks'
+// epilogue, which k_edge_infer of bgcn_ebgcn.hip runs too.  Nothing [E, 64, 64] is ever stored:
+// every pass that needs Y computes it again.
 //
 // Forward (grid.y = network for the two MFMA passes):
 //   k_train_dbar      sum_{e,l} D[e][c][l] per block, valid-edge count, status     (no MFMA)
@@ -32,95 +33,26 @@
 // swapping its operands, and one kernel holding both would need 320 accumulator registers.
 // No float atomics: every cross-block sum goes through per-block partials and a fixed-order
 // second step, so two runs give the same bits.
+#include "bgcn_edge_tile.h"
 #include "bgcn_internal.h"
 
 namespace bgcn {
 namespace {
 
-constexpr int kH = 64;
 constexpr int kTile = 32;           // edges per tile: 4 waves x 8 edges
-constexpr int kMaxEdgeNum = 8;
-constexpr int kWLd = kH + 1;        // LDS row stride of the Wc staging tile
 constexpr int kNets = 5;            // sim, W_mean, W_bias, B_mean, B_bias
 constexpr int kMaxBlocks = 512;     // blocks of a pass (each walks tiles b, b + grid, ...)
 constexpr int kMaxBlocksW = 256;    // blocks of the d_Wc pass (a 16 KB partial each)
-constexpr float kSlope = 0.01f;     // LeakyReLU's default
 
 struct NetW {
   const float* w[kNets];
 };
-
-__device__ __forceinline__ bool edge_ends(const int64_t* __restrict__ ei, int64_t E, int64_t N, int64_t e,
-                                          int64_t& ia, int64_t& ib) {
-  const int64_t row = ei[e], col = ei[E + e];   // wave-uniform
-  if (row < 0 || row >= N || col < 0 || col >= N) return false;
-  ia = row == 0 ? N - 1 : row - 1;   // x[row - 1]: 0 wraps to the last node
-  ib = col == 0 ? N - 1 : col - 1;
-  return true;
-}
-
-// Wc [64][64] -> LDS (all 256 threads), then the A-operand image of the f32 MFMA:
-// lane (r32, hh) holds wa[tt][s] = Wc[32 tt + r32][2 s + hh]
-__device__ __forceinline__ void stage_w(const float* __restrict__ Wc, float* sW) {
-  for (int i = threadIdx.x; i < kH * kH; i += 256) sW[(i >> 6) * kWLd + (i & 63)] = Wc[i];
-}
-__device__ __forceinline__ void load_wa(const float* sW, int r32, int hh, float (&wa)[2][32]) {
-#pragma unroll
-  for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-    for (int s = 0; s < 32; ++s) wa[tt][s] = sW[(32 * tt + r32) * kWLd + 2 * s + hh];
-}
-
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2]) {
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-}
-
-// acc[tt][u][r] = Y[o = 32 tt + 8 (r >> 2) + 4 hh + (r & 3)][l = 32 u + r32]
-__device__ __forceinline__ void y_tile(const float (&wa)[2][32], float av, float b0, float b1, int hh,
-                                       f32x16 (&acc)[2][2]) {
-  zero_acc(acc);
-#pragma unroll
-  for (int s = 0; s < 32; ++s) {
-    const float a = __shfl(av, 2 * s + hh);
-    const float d0 = fabsf(a - b0), d1 = fabsf(a - b1);
-    acc[0][0] = mfma32x32x2(wa[0][s], d0, acc[0][0]);
-    acc[0][1] = mfma32x32x2(wa[0][s], d1, acc[0][1]);
-    acc[1][0] = mfma32x32x2(wa[1][s], d0, acc[1][0]);
-    acc[1][1] = mfma32x32x2(wa[1][s], d1, acc[1][1]);
-  }
-}
-// the same product with the operands swapped: the transpose,
-// acc[tt][u][r] = Y[o = 32 tt + r32][l = 32 u + 8 (r >> 2) + 4 hh + (r & 3)]
-__device__ __forceinline__ void yt_tile(const float (&wa)[2][32], float av, float b0, float b1, int hh,
-                                        f32x16 (&acc)[2][2]) {
-  zero_acc(acc);
-#pragma unroll
-  for (int s = 0; s < 32; ++s) {
-    const float a = __shfl(av, 2 * s + hh);
-    const float d0 = fabsf(a - b0), d1 = fabsf(a - b1);
-    acc[0][0] = mfma32x32x2(d0, wa[0][s], acc[0][0]);
-    acc[0][1] = mfma32x32x2(d1, wa[0][s], acc[0][1]);
-    acc[1][0] = mfma32x32x2(d0, wa[1][s], acc[1][0]);
-    acc[1][1] = mfma32x32x2(d1, wa[1][s], acc[1][1]);
-  }
-}
 
 __device__ __forceinline__ float half_sum(float v) {   // over the 32 lanes that share hh
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float f4at(const float4& v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
 __device__ __forceinline__ float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
 
 // ------------------------------------------------------------------------------- forward
@@ -331,30 +263,10 @@ __global__ __launch_bounds__(256, 2) void k_train_apply(const float* __restrict_
       const float b0 = h[ib * ldh + r32], b1 = h[ib * ldh + 32 + r32];
       f32x16 acc[2][2];
       y_tile(wa, av, b0, b1, hh, acc);
-      float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int o0 = 32 * tt + 8 * q + 4 * hh;
-          const float4 Gv = *reinterpret_cast<const float4*>(&sG[o0]);
-          const float4 Tv = *reinterpret_cast<const float4*>(&sT[o0]);
-          const float4 Ov = *reinterpret_cast<const float4*>(&sO[o0]);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            float z0 = fmaf(f4at(Gv, j), acc[tt][0][4 * q + j], f4at(Tv, j));
-            float z1 = fmaf(f4at(Gv, j), acc[tt][1][4 * q + j], f4at(Tv, j));
-            z0 = fmaxf(z0, kSlope * z0);
-            z1 = fmaxf(z1, kSlope * z1);
-            s0 = fmaf(f4at(Ov, j), z0, s0);
-            s1 = fmaf(f4at(Ov, j), z1, s1);
-          }
-        }
-      s0 += __shfl_xor(s0, 32);
-      s1 += __shfl_xor(s1, 32);
+      const float2 sv = edge_out_sums(acc, sG, sT, sO, hh);
       if (hh == 0) {
-        dst[e * kH + r32] = s0 + bo;
-        dst[e * kH + 32 + r32] = s1 + bo;
+        dst[e * kH + r32] = sv.x + bo;
+        dst[e * kH + 32 + r32] = sv.y + bo;
       }
     }
 }
@@ -941,7 +853,6 @@ __global__ __launch_bounds__(256) void k_train_dh_sum(const int32_t* __restrict_
 }
 
 // ------------------------------------------------------------------------------- host
-bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 int64_t tiles_of(int64_t E) { return (E + kTile - 1) / kTile; }
 int blocks_of(int64_t E, int cap) { return int(std::min<int64_t>(tiles_of(E), cap)); }
 

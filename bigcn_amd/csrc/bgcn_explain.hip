@@ -38,12 +38,6 @@ constexpr int kRankLds = BGCN_SEGMENT_RANK_LDS;
 constexpr int kRankSplit = 8;     // workgroups per (stage, tree) on the counting path
 static_assert((kRankLds & (kRankLds - 1)) == 0 && kRankLds >= 256, "the bitonic network sorts a power of two");
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // sum of the block's 256 values, the same in every thread: butterfly per wave, the four wave
 // sums added in wave order.  sm: 4 floats per call site.
 __device__ __forceinline__ float block_sum(float v, float* sm) {
@@ -280,8 +274,6 @@ size_t carve_rank(Carve& c, int64_t B, RankWs* w) {
   w->bad = w->seg ? w->seg + B + 1 : nullptr;
   return align_up(c.off, 256);
 }
-
-bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

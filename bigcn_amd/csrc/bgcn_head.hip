@@ -16,12 +16,6 @@ namespace {
 
 constexpr int kHeadK = 256;   // cat(BU_x, TD_x) = 4 x 64 (hid = out = 64): lane l holds columns 4l .. 4l+3
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // one wave per tree row, four rows per 256-thread block
 __global__ __launch_bounds__(256) void k_head_fwd(const float* __restrict__ head, const float* __restrict__ W,
                                                   const float* __restrict__ bias, int64_t B, int C,
@@ -95,8 +89,6 @@ __global__ __launch_bounds__(256) void k_head_bwd(const float* __restrict__ head
   dW[int64_t(c) * kHeadK + j] = acc;
   if (j == 0) db[c] = bsum;
 }
-
-bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // The evaluation loop's per-batch reductions (BiGCN_Twitter.py:218-222: val_loss =
 // F.nll_loss(val_out, y); _, val_pred = val_out.max(dim=1); correct = val_pred.eq(y).sum())

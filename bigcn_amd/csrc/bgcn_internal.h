@@ -5,6 +5,8 @@
 
 namespace bgcn {
 
+inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // ---- K3/K4 aggregation (bgcn_spmm.hip)
 struct SpmmProb {
   const int32_t* ptr;
@@ -207,6 +209,44 @@ __device__ __forceinline__ void adam_elem(float& p, float gr, float& m, float& v
   v = fmaf(1.0f - c.b2, __fmul_rn(g, g), __fmul_rn(v, c.b2));   // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
   const float denom = fmaf(sqrtf(v), c.inv_bc2, c.eps);
   p = fmaf(-c.step, __fdiv_rn(m, denom), p);
+}
+// whether a tensor's four arrays can be read and written as float4
+__device__ __forceinline__ bool adam_vec(const float* param, const float* grad, const float* exp_avg,
+                                         const float* exp_avg_sq) {
+  return ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |
+           reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15u) == 0;
+}
+// Four consecutive elements from e of a tensor of numel elements (fewer at its end; none when e
+// is past it): one float4 per array when all four arrays are 16-byte aligned and four elements
+// remain, else element by element.  out (or nullptr) takes the updated parameters, zeros for
+// the elements past the end.
+__device__ __forceinline__ void adam_chunk(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                           int64_t numel, int64_t e, const AdamConst& c, float* out = nullptr) {
+  if (adam_vec(param, grad, exp_avg, exp_avg_sq) && e + 4 <= numel) {
+    float4 p = ld4(param + e), g = ld4(grad + e);
+    float4 m = ld4(exp_avg + e), v = ld4(exp_avg_sq + e);
+    adam_elem(p.x, g.x, m.x, v.x, c);
+    adam_elem(p.y, g.y, m.y, v.y, c);
+    adam_elem(p.z, g.z, m.z, v.z, c);
+    adam_elem(p.w, g.w, m.w, v.w, c);
+    st4(param + e, p);
+    st4(exp_avg + e, m);
+    st4(exp_avg_sq + e, v);
+    if (out) { out[0] = p.x; out[1] = p.y; out[2] = p.z; out[3] = p.w; }
+    return;
+  }
+  for (int j = 0; j < 4; ++j) {
+    float p = 0.f;
+    if (e + j < numel) {
+      float m = exp_avg[e + j], v = exp_avg_sq[e + j];
+      p = param[e + j];
+      adam_elem(p, grad[e + j], m, v, c);
+      param[e + j] = p;
+      exp_avg[e + j] = m;
+      exp_avg_sq[e + j] = v;
+    }
+    if (out) out[j] = p;
+  }
 }
 
 // The optimiser step fused into the backward's tail launch (bgcn_step_args.adam): per step

@@ -18,34 +18,6 @@ namespace {
 constexpr int kChunkElems = 256 * 4;  // elements per block (256 threads x one float4)
 constexpr int H = 64;                  // rows of the conv weights with images
 
-// four consecutive elements from e (vector when the tensor's arrays are 16-byte aligned)
-__device__ __forceinline__ void adam_quad(const bgcn_adam_tensor& T, int64_t e, int n, bool vec,
-                                          const AdamConst& c, float out[4]) {
-  if (vec && n == 4) {
-    float4 p = ld4(T.param + e), g = ld4(T.grad + e);
-    float4 m = ld4(T.exp_avg + e), v = ld4(T.exp_avg_sq + e);
-    adam_elem(p.x, g.x, m.x, v.x, c);
-    adam_elem(p.y, g.y, m.y, v.y, c);
-    adam_elem(p.z, g.z, m.z, v.z, c);
-    adam_elem(p.w, g.w, m.w, v.w, c);
-    st4(T.param + e, p);
-    st4(T.exp_avg + e, m);
-    st4(T.exp_avg_sq + e, v);
-    out[0] = p.x; out[1] = p.y; out[2] = p.z; out[3] = p.w;
-    return;
-  }
-  for (int j = 0; j < 4; ++j) {
-    out[j] = 0.f;
-    if (j >= n) continue;
-    float p = T.param[e + j], m = T.exp_avg[e + j], v = T.exp_avg_sq[e + j];
-    adam_elem(p, T.grad[e + j], m, v, c);
-    T.param[e + j] = p;
-    T.exp_avg[e + j] = m;
-    T.exp_avg_sq[e + j] = v;
-    out[j] = p;
-  }
-}
-
 // A conv weight with a weight image (BGCN_IMAGE_*): tiles of kImgRows rows (o) x kImgCols
 // columns (k), one float4 per thread per pass, every load of the tile issued before the
 // first store; the updated values are staged in LDS and written transposed - W1^T[k][d*64
@@ -72,7 +44,7 @@ static_assert(kImgPasses >= 1 && kImgRpp * kImgPasses == kImgRows && H % kImgRow
                   kImgCols % kImgKpp == 0 && kImgCols >= H, "tile shape");
 constexpr int kImgGroups = H / kImgRows;     // row groups per column tile
 __device__ void adam_image_tile(const bgcn_adam_tensor& T, const AdamConst& c, int role, int64_t tile,
-                                const WeightImages& im, int64_t F, bool vec) {
+                                const WeightImages& im, int64_t F) {
   __shared__ float tl[kImgCols][kImgRows + 1];   // [k][o - o_base]
   const bool w1 = role == BGCN_IMAGE_TD_W1 || role == BGCN_IMAGE_BU_W1;
   const int d = (role == BGCN_IMAGE_BU_W1 || role == BGCN_IMAGE_BU_W2) ? 1 : 0;
@@ -83,7 +55,7 @@ __device__ void adam_image_tile(const bgcn_adam_tensor& T, const AdamConst& c, i
   const int64_t k = k0 + 4 * q;
   const int n = k < K ? int(min<int64_t>(4, K - k)) : 0;
   float u[kImgPasses][4];
-  if (vec && n == 4) {
+  if (adam_vec(T.param, T.grad, T.exp_avg, T.exp_avg_sq) && n == 4) {
     // every pass's loads issued before the first store
     float4 p[kImgPasses], g[kImgPasses], m[kImgPasses], v[kImgPasses];
 #pragma unroll
@@ -101,7 +73,10 @@ __device__ void adam_image_tile(const bgcn_adam_tensor& T, const AdamConst& c, i
     }
   } else {
 #pragma unroll
-    for (int t = 0; t < kImgPasses; ++t) adam_quad(T, int64_t(ob + r + t * kImgRpp) * K + k, n, false, c, u[t]);
+    for (int t = 0; t < kImgPasses; ++t) {   // the row's n elements from k
+      const int64_t e = int64_t(ob + r + t * kImgRpp) * K + k;
+      adam_chunk(T.param, T.grad, T.exp_avg, T.exp_avg_sq, e + n, e, c, u[t]);
+    }
   }
 #pragma unroll
   for (int t = 0; t < kImgPasses; ++t) {
@@ -160,35 +135,11 @@ __global__ __launch_bounds__(256) void k_adam(bgcn_adam_args a, WeightImages im)
                     1.0f / a.bias_correction2_sqrt, a.grad_scale};
   const int role = a.images ? a.image_role[k] : BGCN_IMAGE_NONE;
   if (role != BGCN_IMAGE_NONE) {
-    const bool vec = ((reinterpret_cast<uintptr_t>(T.param) | reinterpret_cast<uintptr_t>(T.grad) |
-                       reinterpret_cast<uintptr_t>(T.exp_avg) |
-                       reinterpret_cast<uintptr_t>(T.exp_avg_sq)) & 15u) == 0;
-    adam_image_tile(T, c, role, int64_t(blockIdx.x) - a.block_start[k], im, a.images_in_feats, vec);
+    adam_image_tile(T, c, role, int64_t(blockIdx.x) - a.block_start[k], im, a.images_in_feats);
     return;
   }
   const int64_t e0 = (int64_t(blockIdx.x) - a.block_start[k]) * kChunkElems + threadIdx.x * 4;
-  const bool vec = ((reinterpret_cast<uintptr_t>(T.param) | reinterpret_cast<uintptr_t>(T.grad) |
-                     reinterpret_cast<uintptr_t>(T.exp_avg) |
-                     reinterpret_cast<uintptr_t>(T.exp_avg_sq)) & 15u) == 0;
-  if (vec && e0 + 4 <= T.numel) {
-    float4 p = ld4(T.param + e0), g = ld4(T.grad + e0);
-    float4 m = ld4(T.exp_avg + e0), v = ld4(T.exp_avg_sq + e0);
-    adam_elem(p.x, g.x, m.x, v.x, c);
-    adam_elem(p.y, g.y, m.y, v.y, c);
-    adam_elem(p.z, g.z, m.z, v.z, c);
-    adam_elem(p.w, g.w, m.w, v.w, c);
-    st4(T.param + e0, p);
-    st4(T.exp_avg + e0, m);
-    st4(T.exp_avg_sq + e0, v);
-    return;
-  }
-  for (int64_t e = e0; e < e0 + 4 && e < T.numel; ++e) {
-    float p = T.param[e], m = T.exp_avg[e], v = T.exp_avg_sq[e];
-    adam_elem(p, T.grad[e], m, v, c);
-    T.param[e] = p;
-    T.exp_avg[e] = m;
-    T.exp_avg_sq[e] = v;
-  }
+  adam_chunk(T.param, T.grad, T.exp_avg, T.exp_avg_sq, T.numel, e0, c);
 }
 
 }  // namespace

@@ -580,8 +580,6 @@ size_t spmm_ws_size(int64_t capacity, int32_t F) {
   return size_t(ngroups) * 2 * size_t(F) * sizeof(float) + 256;
 }
 
-static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 
 // Whether spmm_batch_impl takes K1's plans (k_spmm_rows) for these problems.  The plan pays
 // off while long rows are few and short (one block each): measured on the fused step

@@ -27,7 +27,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from ._lib import check, ptr, stream_handle
+from ._lib import check, ptr, raise_on_status, stream_handle
 from .bigcn import _num_graphs
 from .conv import GCNConv
 from .ops import (_NO_TRAINING, _check_ei, _i64c, build_graph, degree_code, ebgcn_conv2_lin, ebgcn_conv2_lin_train,
@@ -149,8 +149,7 @@ class _EdgeRumorGCN(torch.nn.Module):
 
 
 def _raise_on(status: torch.Tensor) -> None:
-    if int(status.item()) & 1:   # one host sync per forward
-        raise IndexError("the batch holds an edge, root or tree index out of range")
+    raise_on_status(int(status.item()), bits=1)   # one host sync per forward
 
 
 class TDrumorGCN(_EdgeRumorGCN):
@@ -358,7 +357,4 @@ class EBGCN(torch.nn.Module):
             return
         s = int(st["seen"].item())
         st["seen"].zero_()
-        if s & 1:
-            raise IndexError("the batch holds an edge, root or tree index out of range")
-        if s & 2:
-            raise IndexError("the batch holds a label outside [0, num_class)")
+        raise_on_status(s, bits=1 | 2)

@@ -15,7 +15,7 @@ import types
 import torch
 
 from . import _lib
-from ._lib import check, ptr, stream_handle
+from ._lib import check, ptr, raise_on_status, stream_handle
 from .ops import _i64c
 from .optim import MultiAdam, ebgcn_adam
 
@@ -103,10 +103,5 @@ class EBGCNTrainStep:
         _, seen, skipped, _ = st["words"].tolist()
         st["words"][1:3].zero_()
         self.last_skipped = int(skipped)
-        if seen & 8:
-            raise RuntimeError("libbgcn: an internal cross-workgroup hand-off timed out")
-        if seen & 1:
-            raise IndexError(f"the batch holds an edge, root or tree index out of range ({skipped} updates skipped)")
-        if seen & 2:
-            raise IndexError(f"the batch holds a label outside [0, num_class) ({skipped} updates skipped)")
+        raise_on_status(seen, suffix=f" ({skipped} updates skipped)")
         return self.last_skipped

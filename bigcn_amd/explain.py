@@ -21,6 +21,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from ._lib import raise_on_status
 from .bigcn import _num_graphs
 from .ops import (STAGES_BIGCN, STAGES_EBGCN, _segment_rank, build_graph, ebgcn_conv2_lin, edge_infer, explain_sums,
                   gcn_conv, scatter_mean, segment_rank, spmm)
@@ -41,8 +42,8 @@ class DirectionExplanation:
 
 
 def _raise_on(status: torch.Tensor) -> None:
-    if int(status.item()) & 1:   # one host sync per public call
-        raise IndexError("the batch holds an edge, root or tree index out of range, or a batch vector that decreases")
+    # one host sync per public call
+    raise_on_status(int(status.item()), bits=1, index_also=", or a batch vector that decreases")
 
 
 def _batch_of_one_edges(ei, batch, N, B):

@@ -37,27 +37,20 @@ class AdamArgs(ctypes.Structure):
 IMAGE_TD_W1, IMAGE_BU_W1, IMAGE_TD_W2, IMAGE_BU_W2 = 1, 2, 3, 4
 
 
-class FusedAdam:
-    """``param_groups``: list of dicts {"params": [...], "lr": float} (torch layout)."""
+class _AdamBase:
+    """What :class:`FusedAdam` and :class:`MultiAdam` share on the host: the parameter groups (torch
+    layout), the moments, the gradients of a step and the arguments both kernels take."""
 
     def __init__(self, param_groups: Sequence[dict], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0):
-        self.param_groups = []
-        for g in param_groups:
-            ps = [p for p in g["params"]]
-            self.param_groups.append({"params": ps, "lr": g.get("lr", lr)})
+        self.param_groups = [{"params": list(g["params"]), "lr": g.get("lr", lr)} for g in param_groups]
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
         self.step_count = 0
         self.state = {}
         self._cache = None
-        n = sum(len(g["params"]) for g in self.param_groups)
-        if n > MAX_TENSORS:
-            raise ValueError(f"FusedAdam handles at most {MAX_TENSORS} tensors")
-        for g in self.param_groups:
-            for p in g["params"]:
-                if p.dtype != torch.float32 or not p.is_contiguous():
-                    raise ValueError("FusedAdam: contiguous fp32 parameters only")
-                self.state[p] = (torch.zeros_like(p), torch.zeros_like(p))
+        self._keep = []
+        self._check_limits()
+        self._pointer_key(self.params())
 
     def params(self) -> List[torch.nn.Parameter]:
         return [p for g in self.param_groups for p in g["params"]]
@@ -68,6 +61,62 @@ class FusedAdam:
                 p.grad = None
             elif p.grad is not None:
                 p.grad.zero_()
+
+    def _check_param(self, p) -> None:
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise ValueError(f"{type(self).__name__}: contiguous fp32 parameters only")
+
+    def _pointer_key(self, ps):
+        """Every pointer a cached table captures, so that reassigning ``p.data``, swapping a parameter
+        in ``param_groups`` or replacing a moment rebuilds it; a parameter without moments (one
+        added to ``param_groups`` after construction) gets them here."""
+        for p in ps:
+            if p not in self.state:
+                self._check_param(p)
+                self.state[p] = (torch.zeros_like(p), torch.zeros_like(p))
+        return (tuple((p.data_ptr(), p.numel(), self.state[p][0].data_ptr(), self.state[p][1].data_ptr())
+                      for p in ps),
+                tuple(len(g["params"]) for g in self.param_groups))
+
+    def _gradients(self, ps, grads):
+        """One gradient or ``None`` per parameter: ``grads``, else ``p.grad``.  A gradient that is
+        not contiguous is replaced by a contiguous copy, kept alive through the launch."""
+        gs = list(grads) if grads is not None else [p.grad for p in ps]
+        if len(gs) != len(ps):
+            raise ValueError("grads must have one entry per parameter")
+        self._keep = []
+        for k, (p, gr) in enumerate(zip(ps, gs)):
+            if gr is None:
+                continue
+            if gr.dtype != torch.float32 or gr.numel() != p.numel():
+                raise ValueError(f"{type(self).__name__}: a gradient must be fp32 and of its parameter's size")
+            if not gr.is_contiguous():
+                gs[k] = gr.contiguous()
+                self._keep.append(gs[k])
+        return gs
+
+    def _fill_step(self, a, device, grad_scale, skip_flag, skip_count) -> None:
+        """The fields of the next step (step count + 1) that both argument structs have."""
+        if skip_flag is not None and (skip_flag.dtype != torch.float32 or skip_flag.numel() != 1
+                                      or skip_flag.device != device):
+            raise ValueError("skip_flag must be a one-element fp32 tensor on the parameters' device")
+        if skip_count is not None and (skip_count.dtype != torch.int32 or skip_count.numel() != 1):
+            raise ValueError("skip_count must be a one-element int32 tensor")
+        a.skip_flag, a.skip_count = ptr(skip_flag), ptr(skip_count)
+        t = self.step_count + 1
+        b1, b2 = self.betas
+        a.beta1, a.beta2, a.eps, a.weight_decay = b1, b2, self.eps, self.weight_decay
+        a.bias_correction1 = 1.0 - b1 ** t
+        a.bias_correction2_sqrt = math.sqrt(1.0 - b2 ** t)
+        a.grad_scale = grad_scale
+
+
+class FusedAdam(_AdamBase):
+    """``param_groups``: list of dicts {"params": [...], "lr": float} (torch layout)."""
+
+    def _check_limits(self) -> None:
+        if sum(len(g["params"]) for g in self.param_groups) > MAX_TENSORS:
+            raise ValueError(f"FusedAdam handles at most {MAX_TENSORS} tensors")
 
     def step(self, grads: Optional[Sequence[torch.Tensor]] = None, grad_scale: float = 1.0,
              skip_flag: Optional[torch.Tensor] = None, images=None,
@@ -97,78 +146,44 @@ class FusedAdam:
 
         Learning rates are read from ``param_groups`` on every call, so schedulers that
         edit ``group['lr']`` (as with torch.optim.Adam) take effect."""
-        t = self.step_count + 1
-        b1, b2 = self.betas
         ps = self.params()
-        gs = list(grads) if grads is not None else [p.grad for p in ps]
-        # the tensor table (parameter / moment pointers, sizes, groups) is built once per
-        # set of present gradients and parameter / moment storage; only the gradient
-        # pointers are written per step (autograd hands out fresh gradient tensors every
-        # step).  The key holds every pointer the table captures, so reassigning p.data,
-        # swapping a parameter in param_groups or replacing a moment rebuilds it.
-        if len(ps) > MAX_TENSORS:
-            raise ValueError(f"FusedAdam handles at most {MAX_TENSORS} tensors")
-        for p in ps:
-            if p not in self.state:   # a parameter added to param_groups after construction
-                self.state[p] = (torch.zeros_like(p), torch.zeros_like(p))
-        key = (tuple(g is None for g in gs),
-               tuple((p.data_ptr(), p.numel(), self.state[p][0].data_ptr(), self.state[p][1].data_ptr())
-                     for p in ps),
-               tuple(len(g["params"]) for g in self.param_groups))
-        cached = self._cache if getattr(self, "_cache", None) is not None and self._cache[0] == key else None
-        if cached is None:
+        self._check_limits()
+        gs = self._gradients(ps, grads)
+        # the tensor table (parameter / moment pointers, sizes, groups) holds the parameters
+        # with a gradient only and is built once per set of present gradients and pointer key;
+        # only the gradient pointers are written per step (autograd hands out fresh gradient
+        # tensors every step)
+        key = (tuple(g is None for g in gs),) + self._pointer_key(ps)
+        if self._cache is None or self._cache[0] != key:
             a = AdamArgs()
             groups = []         # param_groups index of each table entry (lr refreshed per step)
             entries = []        # params() index of each table entry
-            k = 0
             for gi, p in enumerate(ps):
                 if gs[gi] is None:
                     continue
-                entries.append(gi)
                 m, v = self.state[p]
-                e = a.t[k]
+                e = a.t[len(entries)]
                 e.param, e.exp_avg, e.exp_avg_sq = ptr(p), ptr(m), ptr(v)
                 e.numel = p.numel()
                 groups.append(self._group_of(p))
-                k += 1
-            a.count = k
-            a.beta1, a.beta2, a.eps, a.weight_decay = b1, b2, self.eps, self.weight_decay
-            cached = (key, a, [a.t[k] for k in range(k)], groups, entries)   # entry proxies
-            self._cache = cached
-        keep = []   # non-contiguous gradients: contiguous copies, alive through the launch
-        a, ents, groups = cached[1], cached[2], cached[3]
+                entries.append(gi)
+            a.count = len(entries)
+            self._cache = (key, a, [a.t[k] for k in range(a.count)], groups, entries)   # entry proxies
+        _, a, ents, groups, entries = self._cache
         if a.count == 0:
             return None
-        for e, gi, gj in zip(ents, cached[4], groups):
-            gr = gs[gi]
-            if not gr.is_contiguous():
-                gr = gr.contiguous()
-                keep.append(gr)
-            e.grad = gr.data_ptr()
+        for e, gi, gj in zip(ents, entries, groups):
+            e.grad = gs[gi].data_ptr()
             e.lr = float(self.param_groups[gj]["lr"])
-        if skip_flag is not None:
-            if skip_flag.dtype != torch.float32 or skip_flag.numel() != 1 or skip_flag.device != ps[0].device:
-                raise ValueError("skip_flag must be a one-element fp32 tensor on the parameters' device")
-        a.skip_flag = ptr(skip_flag)
-        if skip_count is not None and (skip_count.dtype != torch.int32 or skip_count.numel() != 1):
-            raise ValueError("skip_count must be a one-element int32 tensor")
-        a.skip_count = ptr(skip_count)
-        a.bias_correction1 = 1.0 - b1 ** t
-        a.bias_correction2_sqrt = math.sqrt(1.0 - b2 ** t)
-        a.grad_scale = grad_scale
+        self._fill_step(a, ps[0].device, grad_scale, skip_flag, skip_count)
         if images is not None:
             buf, F, roles = images
             a.images, a.images_in_feats = ptr(buf), int(F)
-            for k, gi in enumerate(self._entries(cached)):
+            for k, gi in enumerate(entries):
                 a.image_role[k] = roles.get(id(ps[gi]), 0)
         else:
             a.images, a.images_in_feats = None, 0
-        self._keep = keep
         return a
-
-    def _entries(self, cached):
-        """params() index of each table entry (gradients that are None have no entry)."""
-        return cached[4]
 
     def _group_of(self, p) -> int:
         for gi, g in enumerate(self.param_groups):
@@ -181,7 +196,7 @@ MULTI_MAX_TENSORS = _lib.BGCN_ADAM_MULTI_MAX_TENSORS
 MULTI_MAX_GROUPS = _lib.BGCN_ADAM_MULTI_MAX_GROUPS
 
 
-class MultiAdam:
+class MultiAdam(_AdamBase):
     """:class:`FusedAdam`'s interface for up to 128 tensors in up to 8 parameter groups, one launch
     per step (``bgcn_adam_multi_step``, ``csrc/bgcn_adam_multi.hip``); the update has
     ``FusedAdam``'s bits.  ``param_groups``: list of dicts {"params": [...], "lr": float} (torch
@@ -193,46 +208,15 @@ class MultiAdam:
     arguments, so a step copies nothing to the device.  A parameter whose gradient is ``None``
     is left alone (no weight decay either), as by ``torch.optim.Adam``."""
 
-    def __init__(self, param_groups: Sequence[dict], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0):
-        self.param_groups = []
-        for g in param_groups:
-            self.param_groups.append({"params": [p for p in g["params"]], "lr": g.get("lr", lr)})
-        self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
-        self.step_count = 0
-        self.state = {}
-        self._cache = None
-        self._keep = []
-        self._check_limits()
-        for p in self.params():
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise ValueError("MultiAdam: contiguous fp32 parameters only")
-            self.state[p] = (torch.zeros_like(p), torch.zeros_like(p))
-
     def _check_limits(self) -> None:
         if len(self.param_groups) > MULTI_MAX_GROUPS:
             raise ValueError(f"MultiAdam handles at most {MULTI_MAX_GROUPS} parameter groups")
         if sum(len(g["params"]) for g in self.param_groups) > MULTI_MAX_TENSORS:
             raise ValueError(f"MultiAdam handles at most {MULTI_MAX_TENSORS} tensors")
 
-    def params(self) -> List[torch.nn.Parameter]:
-        return [p for g in self.param_groups for p in g["params"]]
-
-    def zero_grad(self, set_to_none: bool = True) -> None:
-        for p in self.params():
-            if set_to_none:
-                p.grad = None
-            elif p.grad is not None:
-                p.grad.zero_()
-
     def _table(self, ps):
         """``(key, args, device table)``, rebuilt when a parameter, a moment or the grouping changed."""
-        for p in ps:
-            if p not in self.state:   # a parameter added to param_groups after construction
-                self.state[p] = (torch.zeros_like(p), torch.zeros_like(p))
-        key = (tuple((p.data_ptr(), p.numel(), self.state[p][0].data_ptr(), self.state[p][1].data_ptr())
-                     for p in ps),
-               tuple(len(g["params"]) for g in self.param_groups))
+        key = self._pointer_key(ps)
         if self._cache is not None and self._cache[0] == key:
             return self._cache
         self._check_limits()
@@ -243,8 +227,7 @@ class MultiAdam:
         k = 0
         for gi, g in enumerate(self.param_groups):
             for p in g["params"]:
-                if not p.is_contiguous() or p.dtype != torch.float32:
-                    raise ValueError("MultiAdam: contiguous fp32 parameters only")
+                self._check_param(p)
                 m, v = self.state[p]
                 e = entries[k]
                 e.param, e.exp_avg, e.exp_avg_sq = ptr(p), ptr(m), ptr(v)
@@ -268,37 +251,13 @@ class MultiAdam:
         if not ps:
             self.step_count += 1
             return
-        gs = list(grads) if grads is not None else [p.grad for p in ps]
-        if len(gs) != len(ps):
-            raise ValueError("grads must have one entry per parameter")
+        gs = self._gradients(ps, grads)
         _, a, _ = self._table(ps)
-        t = self.step_count + 1
-        b1, b2 = self.betas
-        keep = []   # non-contiguous gradients: contiguous copies, alive through the launch
-        grad = a.grad
-        for k, (p, gr) in enumerate(zip(ps, gs)):
-            if gr is None:
-                grad[k] = None
-                continue
-            if gr.dtype != torch.float32 or gr.numel() != p.numel():
-                raise ValueError("MultiAdam: a gradient must be fp32 and of its parameter's size")
-            if not gr.is_contiguous():
-                gr = gr.contiguous()
-                keep.append(gr)
-            grad[k] = gr.data_ptr()
+        for k, gr in enumerate(gs):
+            a.grad[k] = None if gr is None else gr.data_ptr()
         for gi, g in enumerate(self.param_groups):
             a.lr[gi] = float(g["lr"])
-        if skip_flag is not None and (skip_flag.dtype != torch.float32 or skip_flag.numel() != 1
-                                      or skip_flag.device != ps[0].device):
-            raise ValueError("skip_flag must be a one-element fp32 tensor on the parameters' device")
-        if skip_count is not None and (skip_count.dtype != torch.int32 or skip_count.numel() != 1):
-            raise ValueError("skip_count must be a one-element int32 tensor")
-        a.skip_flag, a.skip_count = ptr(skip_flag), ptr(skip_count)
-        a.beta1, a.beta2, a.eps, a.weight_decay = b1, b2, self.eps, self.weight_decay
-        a.bias_correction1 = 1.0 - b1 ** t
-        a.bias_correction2_sqrt = math.sqrt(1.0 - b2 ** t)
-        a.grad_scale = grad_scale
-        self._keep = keep
+        self._fill_step(a, ps[0].device, grad_scale, skip_flag, skip_count)
         self.step_count += 1
         check(_lib.lib().bgcn_adam_multi_step(ctypes.addressof(a), stream_handle()))
 

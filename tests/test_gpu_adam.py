@@ -19,7 +19,7 @@ grad_scale >= 0.125), so the comparison does not depend on how subnormal interme
 Paths (k_adam): a tensor without an image role takes the float4 path when all four arrays are
 16-byte aligned and the quad lies inside it, else the scalar loop; a tensor with an image role runs
 adam_image_tile, float4 when aligned and the quad lies inside the row (always, K % 4 == 0), else
-adam_quad's scalar loop.
+adam_chunk's scalar loop.
 """
 import ctypes
 
@@ -271,7 +271,7 @@ def test_image_tensors(F):
 
 @pytest.mark.parametrize("F", [4, 132])
 def test_image_tensors_with_misaligned_gradients(F):
-    """adam_quad's scalar loop inside adam_image_tile."""
+    """adam_chunk's scalar loop inside adam_image_tile."""
     C = ImageCase(F, seed=1, grad_lead=1)
     C.step()
     C.check("step 1")
