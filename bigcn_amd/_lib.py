@@ -41,6 +41,9 @@ BGCN_RANK_SIMILARITY_MAX = 32   # most rankings, and the largest k, of bgcn_rank
 BGCN_STATUS_TWO_PARENTS = 32
 BGCN_STATUS_CYCLE = 64
 BGCN_STATUS_BATCH_UNSORTED = 128   # bgcn_ebgcn_eval_step: the batch vector is not sorted (information)
+BGCN_STATUS_SEQUENCE = 256   # bgcn_lstm_eval: a bad sequence start, a sequence over max_len, a bad label
+BGCN_LSTM_SEQ_TILE = 32   # sequences per workgroup of a step launch of bgcn_lstm_eval
+BGCN_LSTM_MAX_LAYERS = 4
 
 # every symbol include/bgcn.h declares (checked by tests/test_capi.py)
 EXPORTED_SYMBOLS = (
@@ -69,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "bgcn_edge_infer_train_workspace_size", "bgcn_edge_infer_train_fwd", "bgcn_edge_infer_train_bwd",
     "bgcn_ebgcn_conv2_lin_train_workspace_size", "bgcn_ebgcn_conv2_lin_train_fwd", "bgcn_ebgcn_conv2_lin_train_bwd",
     "bgcn_adam_multi_table_size", "bgcn_adam_multi_plan", "bgcn_adam_multi_step", "bgcn_ebgcn_train_loss",
+    "bgcn_lstm_workspace_size", "bgcn_lstm_eval",
 )
 
 BGCN_ADAM_MULTI_MAX_TENSORS = 128
@@ -190,6 +194,19 @@ class EbgcnEvalArgs(Structure):
 class EbgcnEvalView(Structure):
     """bgcn_ebgcn_eval_view (include/bgcn.h)."""
     _fields_ = [("t_ptr", c_void_p), ("t_col", c_void_p), ("t_w", c_void_p), ("t_w2", c_void_p), ("slot", c_void_p)]
+
+
+class LstmArgs(Structure):
+    """bgcn_lstm_args (include/bgcn.h)."""
+    _fields_ = [
+        ("x", c_void_p), ("ldx", c_int64), ("num_nodes", c_int64), ("in_feats", c_int64), ("hid", c_int64),
+        ("num_layers", c_int64), ("out_feats", c_int64),
+        ("seq_start", c_void_p), ("num_seqs", c_int64), ("max_len", c_int64),
+        ("w_ih", (c_void_p * 2) * BGCN_LSTM_MAX_LAYERS), ("w_hh", (c_void_p * 2) * BGCN_LSTM_MAX_LAYERS),
+        ("fc_w", c_void_p), ("fc_b", c_void_p), ("y", c_void_p),
+        ("logp", c_void_p), ("h_n", c_void_p), ("out", c_void_p), ("loss", c_void_p), ("correct", c_void_p),
+        ("pred", c_void_p), ("status", c_void_p),
+    ]
 
 
 class EdgeNet(Structure):
@@ -357,6 +374,8 @@ _SIGS = {
     "bgcn_ebgcn_train_loss": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_float, c_float,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
+    "bgcn_lstm_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64]),
+    "bgcn_lstm_eval": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

@@ -1130,6 +1130,74 @@ typedef struct bgcn_loader_stats {
 int bgcn_loader_get_stats(void* handle, bgcn_loader_stats* out, int reset);
 void bgcn_loader_destroy(void* handle);
 
+/* --------------------------------------------------------------------------
+ * LSTM baseline, evaluation: the test loop body of model/Twitter/LSTM_Twitter.py:146-173
+ *   for each tree: val_out[b] = model(cls[rootindex[b] : rootindex[b + 1]])   (the last to N)
+ *   val_loss = F.nll_loss(val_out, y); _, val_pred = val_out.max(dim=1); correct = ...
+ * for a whole batch of trees as one call: one launch sequence, no host round trip, no allocation
+ * (everything lives in the caller's workspace).  Additive entry points: BGCN_ABI_VERSION is
+ * unchanged.
+ *
+ * The model is nn.LSTM(in_feats, hid, num_layers, batch_first, bidirectional, bias = False) and
+ * fc = nn.Linear(2 * num_layers * hid, out_feats).  w_ih[l][d] / w_hh[l][d] are weight_ih_l{l} /
+ * weight_hh_l{l} (d = 1: the _reverse ones): [4 hid, K_l] and [4 hid, hid], K_0 = in_feats,
+ * K_l = 2 hid, gate rows in the order i, f, g, o; c' = sig(f) c + sig(i) tanh(g),
+ * h = sig(o) tanh(c'), h0 = c0 = 0.  Sequence b is the rows [seq_start[b], seq_start[b + 1]) of
+ * x (the last one runs to num_nodes); the reverse direction runs over each sequence's own length.
+ * Per layer one GEMM gives both directions' input projections G [N, 8 hid]; then one launch per
+ * time step s < max_len covers both directions and every sequence still running (forward: row
+ * start + s, reverse: row start + len - 1 - s), reading h of the previous step from the layer
+ * output Y_l [N, 2 hid] (forward in columns [0, hid), reverse in [hid, 2 hid)) and writing its
+ * own row there; stream order is the only dependency between the launches.  h_n is ordered
+ * (l0 fwd, l0 rev, l1 fwd, ...): a forward direction's final state is Y_l at the sequence's last
+ * row, a reverse direction's at its first.  logp = log_softmax(fc(h_n of the sequence, flattened
+ * in that order)); with y, loss = the mean NLL, pred = the first maximal class (torch's max),
+ * correct = the number of sequences with pred == y; without y, loss and correct are 0.  Rows of x
+ * before seq_start[0] belong to no sequence: their rows of every Y_l (and of `out`) are zeros.
+ * Deterministic: no float atomics, fixed summation orders.
+ *
+ * Validity is decided on the device.  *status is zeroed by the call; BGCN_STATUS_SEQUENCE is set by
+ * a seq_start that does not increase strictly, a start outside [0, num_nodes), a sequence longer
+ * than max_len (max_len is the number of step launches: the caller's bound, never a truncation),
+ * or a label outside [0, out_feats).  A fault in seq_start or max_len empties every sequence of the
+ * batch: no step runs, every final state is zero, nothing out of bounds is read or written and
+ * the results are not to be used; a bad label contributes no loss.
+ *
+ * BGCN_EINVAL before any HIP call: in_feats not a positive multiple of 4, hid not a multiple of 64
+ * in [64, 1024], num_layers outside [1, 4] ("unsupported shape"; bgcn_lstm_workspace_size returns
+ * 0 for these), out_feats outside [1, 64], max_len < 1, a null x / seq_start / weight / fc /
+ * logp / status, x, ldx or a weight not 16-byte aligned, "workspace too small".
+ * -------------------------------------------------------------------------- */
+#define BGCN_STATUS_SEQUENCE 256
+#define BGCN_LSTM_SEQ_TILE 32    /* sequences per workgroup of a step launch */
+typedef struct bgcn_lstm_args {
+  const float* x;                /* [N, ldx] fp32, in_feats columns used     */
+  int64_t ldx;
+  int64_t num_nodes;             /* N                                        */
+  int64_t in_feats;
+  int64_t hid;                   /* H                                        */
+  int64_t num_layers;            /* L                                        */
+  int64_t out_feats;             /* C                                        */
+  const int64_t* seq_start;      /* [B] first row of each sequence           */
+  int64_t num_seqs;              /* B                                        */
+  int64_t max_len;               /* step launches per layer                  */
+  const float* w_ih[4][2];       /* [layer][direction]: [4H, K_l]            */
+  const float* w_hh[4][2];       /* [4H, H]                                  */
+  const float* fc_w;             /* [C, 2 L H]                               */
+  const float* fc_b;             /* [C]                                      */
+  const int64_t* y;              /* [B] labels, or NULL                      */
+  float* logp;                   /* [B, C]                                   */
+  float* h_n;                    /* [2 L, B, H] or NULL                      */
+  float* out;                    /* [N, 2H] last layer's output, or NULL     */
+  float* loss;                   /* [1] mean NLL, or NULL                    */
+  int32_t* correct;              /* [1] or NULL                              */
+  int64_t* pred;                 /* [B] or NULL                              */
+  int32_t* status;               /* [1]                                      */
+} bgcn_lstm_args;
+size_t bgcn_lstm_workspace_size(int64_t num_nodes, int64_t num_seqs, int64_t in_feats, int64_t hid,
+                                int64_t num_layers);
+int bgcn_lstm_eval(const bgcn_lstm_args* args, void* workspace, size_t workspace_bytes, bgcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
