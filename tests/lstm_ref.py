@@ -1,7 +1,8 @@
 """The reference's LSTM baseline restated (model/Twitter/LSTM_Twitter.py:19-49 and the test loop
 :146-173): ``torch.nn.LSTM`` + ``Linear`` on the CPU, looped over the trees one sequence at a time
 exactly as the reference does, in fp64 (the oracle) or fp32 (the reference's own arithmetic).
-Also the seeded case generator shared by tests/test_lstm.py and tests/test_gpu_lstm.py."""
+Also the seeded case generators shared by tests/test_lstm.py, tests/test_gpu_lstm.py (CASES) and
+tests/test_gpu_lstm_edges.py (EDGE_CASES)."""
 import functools
 from types import SimpleNamespace
 
@@ -95,11 +96,29 @@ CASES = {
 }
 
 
-@functools.lru_cache(maxsize=None)
-def case(name):
-    """The seeded inputs of a case and its fp64 oracle, computed once and shared (read-only)."""
-    c = CASES[name]
-    seed = sorted(CASES).index(name) + 1
+# ---- the edge cases of tests/test_gpu_lstm_edges.py: shapes the table above does not reach.  Each
+# entry carries its own seed (case() derives a seed from the name's position in sorted(CASES), so
+# CASES itself must not grow: a new name there would change every existing case's data).
+EDGE_CASES = {
+    # B = 300 > 256: the second iteration of the setup's and the finish's loops over B; 10 sequence tiles
+    "many_trees": dict(in_feats=8, hid=64, layers=1, out=4, lengths=[1 + b % 3 for b in range(300)], seed=101),
+    # two and four iterations of a wave's k loop in the step
+    "hid_128": dict(in_feats=12, hid=128, layers=2, out=5, lengths=[1, 5, 18, 2], seed=112),
+    "hid_256": dict(in_feats=12, hid=256, layers=1, out=3, lengths=[1, 7, 3], seed=103),
+    # the largest configuration the entry point takes: the head's h_n holds 2 L H = 8192 values
+    "largest": dict(in_feats=4, hid=1024, layers=4, out=3, lengths=[2, 1, 3], seed=104),
+    # N = 8217 rows: both layers' input GEMMs run on the six-product kernel (8192 rows and more)
+    "rows_over_switch": dict(in_feats=20, hid=64, layers=2, out=4,
+                             lengths=[1 + (37 * b) % 129 for b in range(126)], seed=105),
+    "one_class": dict(in_feats=8, hid=64, layers=1, out=1, lengths=[1, 4, 2], seed=106),
+    "classes_63": dict(in_feats=8, hid=64, layers=1, out=63, lengths=[1, 4, 2], seed=107),
+    # rows above the first start, more than one sequence tile
+    "offset_many": dict(in_feats=8, hid=64, layers=2, out=4, lengths=[1 + b % 4 for b in range(40)], first=5,
+                        seed=108),
+}
+
+
+def _make(name, c, seed):
     g = torch.Generator().manual_seed(seed)
     first = c.get("first", 0)
     N = first + sum(c["lengths"])
@@ -116,6 +135,19 @@ def case(name):
     ref = run(lstm, fc, x, rootindex, y)
     return SimpleNamespace(name=name, cfg=c, seed=seed, x=x, rootindex=rootindex, y=y, N=N, B=len(starts),
                            max_len=max(c["lengths"]), weight_factor=factor, sd=state_dict(lstm, fc), ref=ref)
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """The seeded inputs of a case and its fp64 oracle, computed once and shared (read-only)."""
+    return _make(name, CASES[name], sorted(CASES).index(name) + 1)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(name):
+    """As case(), for EDGE_CASES and the entry's own seed."""
+    c = EDGE_CASES[name]
+    return _make(name, c, c["seed"])
 
 
 def margin_ok(logp, gap=1e-3):
