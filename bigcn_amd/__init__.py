@@ -23,10 +23,13 @@ Drop-in symbols for the reference's hot path (cwkd/BiGCN):
   predictions on the device, ``class_metrics`` / ``evaluation4class`` / ``evaluationclass`` give the
   reference's numbers from the counts, ``EpochMetrics`` records a validation epoch without a host sync
   (``FusedTrainStep.validate`` is the reference's test loop around it)
-* ``LSTM`` - the PHEME comparison's LSTM baseline (model/Twitter/LSTM_Twitter.py), evaluation: a whole
+* ``LSTM`` - the PHEME comparison's LSTM baseline (model/Twitter/LSTM_Twitter.py): a whole
   batch of trees per native call (``bgcn_lstm_eval``: one GEMM per layer for both directions' input
   projections, one launch per time step for every tree), reference checkpoints load strictly;
   ``LSTM.evaluate`` / ``LSTM.validate`` are the reference's test loop
+* ``LSTMTrainStep`` / ``lstm_adam`` - the LSTM baseline's training-loop body (LSTM_Twitter.py:96-126):
+  forward, loss and backpropagation through time as one native call (``bgcn_lstm_train_grad``,
+  also ``LSTM.grad_batch``), then the reference's Adam as one ``MultiAdam`` launch
 * ``FusedTrainStep`` - the training-loop body (BiGCN_Twitter.py:183-189) as one native call
   + the data-parallel all-reduce + fused Adam
 
@@ -37,7 +40,7 @@ from .conv import GCNConv
 from .compare import compare, rank_similarity, tree_centrality
 from .ebgcn import EBGCN
 from .explain import explain, segment_rank
-from .lstm import LSTM
+from .lstm import LSTM, LSTMTrainStep, lstm_adam
 from . import metrics
 from .metrics import EpochMetrics, class_metrics, confusion, evaluation4class, evaluationclass
 from .ops import (Graph, bigcn_encoder, build_graph, ebgcn_conv2_lin_train, edge_infer, edge_infer_train,
@@ -53,6 +56,6 @@ __all__ = ["GCNConv", "scatter_mean", "TDrumorGCN", "BUrumorGCN", "BiGCN", "Net"
            "MultiAdam", "ebgcn_adam", "EBGCNTrainStep", "drop_edges",
            "explain", "segment_rank",
            "compare", "tree_centrality", "rank_similarity",
-           "LSTM",
+           "LSTM", "LSTMTrainStep", "lstm_adam",
            "metrics", "confusion", "class_metrics", "evaluation4class", "evaluationclass", "EpochMetrics"]
 __version__ = "0.1.0"

@@ -72,7 +72,7 @@ EXPORTED_SYMBOLS = (
     "bgcn_edge_infer_train_workspace_size", "bgcn_edge_infer_train_fwd", "bgcn_edge_infer_train_bwd",
     "bgcn_ebgcn_conv2_lin_train_workspace_size", "bgcn_ebgcn_conv2_lin_train_fwd", "bgcn_ebgcn_conv2_lin_train_bwd",
     "bgcn_adam_multi_table_size", "bgcn_adam_multi_plan", "bgcn_adam_multi_step", "bgcn_ebgcn_train_loss",
-    "bgcn_lstm_workspace_size", "bgcn_lstm_eval",
+    "bgcn_lstm_workspace_size", "bgcn_lstm_eval", "bgcn_lstm_train_workspace_size", "bgcn_lstm_train_grad",
 )
 
 BGCN_ADAM_MULTI_MAX_TENSORS = 128
@@ -206,6 +206,15 @@ class LstmArgs(Structure):
         ("fc_w", c_void_p), ("fc_b", c_void_p), ("y", c_void_p),
         ("logp", c_void_p), ("h_n", c_void_p), ("out", c_void_p), ("loss", c_void_p), ("correct", c_void_p),
         ("pred", c_void_p), ("status", c_void_p),
+    ]
+
+
+class LstmTrainArgs(Structure):
+    """bgcn_lstm_train_args (include/bgcn.h)."""
+    _fields_ = [
+        ("fwd", LstmArgs),
+        ("d_w_ih", (c_void_p * 2) * BGCN_LSTM_MAX_LAYERS), ("d_w_hh", (c_void_p * 2) * BGCN_LSTM_MAX_LAYERS),
+        ("d_fc_w", c_void_p), ("d_fc_b", c_void_p), ("dx", c_void_p), ("skip_flag", c_void_p),
     ]
 
 
@@ -376,6 +385,8 @@ _SIGS = {
                                       c_void_p]),
     "bgcn_lstm_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64]),
     "bgcn_lstm_eval": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "bgcn_lstm_train_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64]),
+    "bgcn_lstm_train_grad": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

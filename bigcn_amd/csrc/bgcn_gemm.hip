@@ -31,7 +31,8 @@ __device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (
 // ============================================================================
 // BKM = false: W is [Nc, K] (Y = X W^T, GCNConv.lin forward);
 // BKM = true : W is [K, Nc] (Y = X W, the input gradient dX = dZ W of GCNConv.lin),
-//              staged k-major in LDS.  W1/split are ignored for BKM.
+//              staged k-major in LDS; rows k < split come from W0, the others from W1 (two
+//              row-stacked tensors: dX = dG [W_fwd ; W_rev] of the LSTM's input projections).
 template <bool VEC, bool BKM, class TX = float>
 __global__ __launch_bounds__(256) void k_gemm_xwt(const TX* __restrict__ X, int64_t ldx,
                                                   const float* __restrict__ W0,
@@ -86,12 +87,13 @@ __global__ __launch_bounds__(256) void k_gemm_xwt(const TX* __restrict__ X, int6
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         int64_t kk = k0 + bk_k + 8 * i, n = n0 + bk_n;
+        const float* wk = kk < split ? W0 + kk * ldw : W1 + (kk - split) * ldw;
         if (VEC) {
-          rb[i] = (kk < K && n < Nc) ? ld4(W0 + kk * ldw + n) : f4zero();
+          rb[i] = (kk < K && n < Nc) ? ld4(wk + n) : f4zero();
         } else {
           float t[4];
 #pragma unroll
-          for (int j = 0; j < 4; ++j) t[j] = (kk < K && n + j < Nc) ? W0[kk * ldw + n + j] : 0.f;
+          for (int j = 0; j < 4; ++j) t[j] = (kk < K && n + j < Nc) ? wk[n + j] : 0.f;
           rb[i] = make_float4(t[0], t[1], t[2], t[3]);
         }
       }
@@ -1047,23 +1049,29 @@ int gemm_xwt_x(const void* X, int xdt, int64_t ldx, const float* W0, const float
                     stream, gate);
 }
 
-int gemm_xw_impl(const float* X, int64_t ldx, const float* W, int64_t ldw, float* Y, int64_t ldy,
-                 int64_t M, int64_t Nc, int64_t K, hipStream_t stream) {
-  BGCN_CHECK_ARG(X && W && Y, "null pointer");
+int gemm_xw2_impl(const float* X, int64_t ldx, const float* W0, const float* W1, int64_t ldw, int64_t split,
+                  float* Y, int64_t ldy, int64_t M, int64_t Nc, int64_t K, hipStream_t stream) {
+  BGCN_CHECK_ARG(X && W0 && Y, "null pointer");
   BGCN_CHECK_ARG(M >= 0 && Nc > 0 && K > 0, "bad shape");
   BGCN_CHECK_ARG(ldx >= K && ldw >= Nc && ldy >= Nc, "bad leading dimension");
+  BGCN_CHECK_ARG(split >= K || W1, "W1 required when split < K");
   if (M == 0) return BGCN_OK;
   bool vec = K % 4 == 0 && Nc % 4 == 0 && ldx % 4 == 0 && ldw % 4 == 0 && aligned16(X) &&
-             aligned16(W);
+             aligned16(W0) && (split >= K || aligned16(W1));
   dim3 grid(grid_for(M, 64), grid_for(Nc, 128));
   if (vec)
-    hipLaunchKernelGGL((k_gemm_xwt<true, true>), grid, dim3(256), 0, stream, X, ldx, W,
-                       (const float*)nullptr, ldw, Nc, Y, ldy, M, Nc, K, (const int32_t*)nullptr);
+    hipLaunchKernelGGL((k_gemm_xwt<true, true>), grid, dim3(256), 0, stream, X, ldx, W0, W1, ldw, split, Y, ldy, M,
+                       Nc, K, (const int32_t*)nullptr);
   else
-    hipLaunchKernelGGL((k_gemm_xwt<false, true>), grid, dim3(256), 0, stream, X, ldx, W,
-                       (const float*)nullptr, ldw, Nc, Y, ldy, M, Nc, K, (const int32_t*)nullptr);
+    hipLaunchKernelGGL((k_gemm_xwt<false, true>), grid, dim3(256), 0, stream, X, ldx, W0, W1, ldw, split, Y, ldy, M,
+                       Nc, K, (const int32_t*)nullptr);
   BGCN_CHECK_LAUNCH();
   return BGCN_OK;
+}
+
+int gemm_xw_impl(const float* X, int64_t ldx, const float* W, int64_t ldw, float* Y, int64_t ldy,
+                 int64_t M, int64_t Nc, int64_t K, hipStream_t stream) {
+  return gemm_xw2_impl(X, ldx, W, nullptr, ldw, K, Y, ldy, M, Nc, K, stream);
 }
 
 // ---------------------------------------------------------------- column sums

@@ -71,6 +71,10 @@ int gemm_tn_impl(const float* G, int64_t ldg, const float* X, int64_t ldx, float
                  int64_t ldc, int64_t split, int64_t Mc, int64_t Nc, int64_t K, void* ws,
                  size_t ws_bytes, hipStream_t stream, int timing_cls, const int32_t* gate);
 size_t tn_ws_size(int64_t Mc, int64_t Nc, int64_t K);
+// Y[M, Nc] = X[M, K] . [W0 ; W1]: W0 [split, Nc] over W1 [K - split, Nc], both with stride ldw
+// (bgcn_gemm_xw is the one-tensor form, split = K)
+int gemm_xw2_impl(const float* X, int64_t ldx, const float* W0, const float* W1, int64_t ldw, int64_t split,
+                  float* Y, int64_t ldy, int64_t M, int64_t Nc, int64_t K, hipStream_t stream);
 // the same GEMMs with the node features X as fp32 or bf16 (xdt: BGCN_DTYPE_*)
 // fp32 X takes the six-product bf16-MFMA kernels (128-row tiles, about one block per CU)
 // only from this many rows on: at PHEME's ~1.2k nodes per batch their 10-20 blocks leave the

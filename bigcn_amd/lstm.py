@@ -1,12 +1,18 @@
-"""The LSTM baseline of the PHEME comparison (``model/Twitter/LSTM_Twitter.py``), evaluation only.
+"""The LSTM baseline of the PHEME comparison (``model/Twitter/LSTM_Twitter.py``).
 
 ``LSTM`` is the reference's module key for key (``lstm.weight_ih_l0`` ... ``fc.bias``), so a
 checkpoint's ``model_state_dict`` loads with ``strict=True``.  The reference calls ``nn.LSTM`` once
 per tree inside a Python loop; here a whole batch of trees goes through one native call
 (``bgcn_lstm_eval``): per layer one GEMM for both directions' input projections and one launch per
 time step for every tree at once.  ``torch.nn.LSTM`` only holds the parameters; its forward is
-never called.  Training (backpropagation through time, the weight gradients and Adam over the
-LSTM's tensors) is not built yet: ``forward`` raises in training mode.
+never called.
+
+Training: :meth:`LSTM.grad_batch` is the loop body's forward, loss and backward for a whole batch
+as one native call (``bgcn_lstm_train_grad``: the same forward keeping the gates and cell states,
+backpropagation through time with one launch per time step, GEMMs for the weight gradients), and
+:class:`LSTMTrainStep` adds the reference's Adam (:func:`bigcn_amd.lstm_adam`) with no host sync
+besides ``max_len``'s.  The per-tree ``forward`` stays an evaluation call and raises in training
+mode: there is no autograd path through it.
 """
 from __future__ import annotations
 
@@ -15,7 +21,8 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import check, ptr, stream_handle
+from ._lib import check, ptr, raise_on_status, stream_handle
+from .optim import MultiAdam
 
 
 def max_sequence_len(rootindex, num_nodes: int) -> int:
@@ -138,14 +145,96 @@ class LSTM(torch.nn.Module):
         st["seen"].bitwise_or_(st["status"])   # the call zeroes its status word; check_status reads this one
         return {"logp": logp, "loss": loss, "correct": correct, "pred": pred, "out": out, "h_n": h_n}
 
+    def names(self):
+        """The ``state_dict`` names in the order of the native call's tensors (:meth:`_tensors`)."""
+        out = []
+        for kind in ("weight_ih", "weight_hh"):
+            for l in range(self.num_layers):
+                out += [f"lstm.{kind}_l{l}", f"lstm.{kind}_l{l}_reverse"]
+        return out + ["fc.weight", "fc.bias"]
+
+    def _train(self, x, rootindex, y, max_len, dx=False, grads=None, want_pred=False, skip_flag=None):
+        """One ``bgcn_lstm_train_grad`` call.  ``grads``: fp32 contiguous buffers in :meth:`names`
+        order (default: new ones)."""
+        if not x.is_cuda:
+            raise _lib.BGCNError("bigcn_amd ops take device tensors (no CPU path)")
+        if x.dim() != 2 or x.size(1) != self.in_feats:
+            raise ValueError(f"the sequences' rows must be [N, {self.in_feats}], got {tuple(x.shape)}")
+        dev = x.device
+        st = self._bind(dev)
+        if not (x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+                and x.stride(0) >= x.size(1)):
+            x = x.float().contiguous()
+        rootindex = rootindex.to(device=dev, dtype=torch.int64).contiguous()
+        N, B, H, L, C = int(x.size(0)), int(rootindex.numel()), self.hid_feats, self.num_layers, self.out_feats
+        if N < 1 or B < 1:
+            raise ValueError("the batch needs at least one row and one tree")
+        y = y.to(device=dev, dtype=torch.int64).contiguous()
+        if y.numel() != B:
+            raise ValueError("y must have one label per tree")
+        if max_len is None:
+            max_len = max_sequence_len(rootindex, N)
+        lib = _lib.lib()
+        sizes = (N, B)
+        if st.get("tsizes") != sizes:
+            need = lib.bgcn_lstm_train_workspace_size(N, B, self.in_feats, H, L)
+            if need == 0:
+                raise _lib.BGCNError("bgcn_lstm_train_grad: unsupported shape (in_feats % 4, hid_feats % 64 in "
+                                     "[64, 1024], num_layers in [1, 4])")
+            if st.get("tws") is None or st["tws"].numel() < need or st["tws"].device != dev:
+                st["tws"] = _lib.workspace(need, dev)
+            st["tsizes"] = sizes
+        ws = st["tws"]
+        if grads is None:
+            grads = [torch.empty(t.shape, dtype=torch.float32, device=dev) for t in st["held"]]
+        if skip_flag is None:
+            skip_flag = torch.empty(1, dtype=torch.float32, device=dev)
+        logp = torch.empty(B, C, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        correct = torch.empty(1, dtype=torch.int32, device=dev)
+        pred = torch.empty(B, dtype=torch.int64, device=dev) if want_pred else None
+        gx = torch.empty(N, x.stride(0), dtype=torch.float32, device=dev) if dx else None
+        ta = st.get("targs")
+        if ta is None:
+            ta = st["targs"] = _lib.LstmTrainArgs()
+        ctypes.memmove(ctypes.addressof(ta.fwd), ctypes.addressof(st["args"]), ctypes.sizeof(_lib.LstmArgs))
+        a = ta.fwd
+        a.x, a.ldx, a.num_nodes = x.data_ptr(), x.stride(0), N
+        a.seq_start, a.num_seqs, a.max_len = rootindex.data_ptr(), B, int(max_len)
+        a.y, a.logp, a.h_n, a.out = y.data_ptr(), logp.data_ptr(), None, None
+        a.loss, a.correct, a.pred = loss.data_ptr(), correct.data_ptr(), ptr(pred)
+        for l in range(L):
+            for d in range(2):
+                ta.d_w_ih[l][d] = grads[2 * l + d].data_ptr()
+                ta.d_w_hh[l][d] = grads[2 * L + 2 * l + d].data_ptr()
+        ta.d_fc_w, ta.d_fc_b = grads[4 * L].data_ptr(), grads[4 * L + 1].data_ptr()
+        ta.dx, ta.skip_flag = ptr(gx), skip_flag.data_ptr()
+        check(lib.bgcn_lstm_train_grad(ctypes.addressof(ta), ptr(ws), ws.numel(), stream_handle()))
+        st["seen"].bitwise_or_(st["status"])
+        return {"logp": logp, "loss": loss, "correct": correct, "pred": pred, "grads": grads,
+                "dx": None if gx is None else gx[:, :self.in_feats], "skip_flag": skip_flag}
+
+    def grad_batch(self, x, rootindex, y, max_len=None, dx=False):
+        """Forward, mean NLL loss and backward of one batch of trees (``LSTM_Twitter.py:96-124`` up to
+        ``optimizer.step()``) as one native call: ``(loss, correct, grads)``, 0-dim fp32 / int32 device
+        tensors and a dict of the loss's gradients keyed by the ``state_dict`` names, plus ``"x"``
+        (``[N, in_feats]``) with ``dx=True``.  New tensors on every call; ``.grad`` is not touched.
+        ``max_len``: as :meth:`forward_batch` (``None`` = the call's one host read).  Validity:
+        :meth:`check_status`; the gradients of a flagged batch are not to be used."""
+        r = self._train(x, rootindex, y, max_len, dx=dx)
+        grads = dict(zip(self.names(), r["grads"]))
+        if dx:
+            grads["x"] = r["dx"]
+        return r["loss"].view(()), r["correct"].view(()), grads
+
     def forward(self, data):
         """The reference's per-tree call: ``data`` is one tree's rows, ``[n, in_feats]`` when
         ``version == 2``, else ``[n, T, in_feats]`` pooled over ``T``.  Returns ``[1, out_feats]`` log
         probabilities, on the kernels of :meth:`forward_batch` as a batch of one tree (no host sync)."""
         if self.training:
-            raise NotImplementedError("bigcn_amd.LSTM runs in eval mode only: the training follow-up "
-                                      "(backpropagation through time, the weight gradients, Adam) is not built; "
-                                      "call model.eval()")
+            raise NotImplementedError("bigcn_amd.LSTM.forward is the per-tree evaluation call and has no autograd "
+                                      "path: for training use bigcn_amd.LSTMTrainStep(model).step(batch) (or "
+                                      "LSTM.grad_batch), else call model.eval()")
         x = data if self.version == 2 else self._pool(data)
         if x.dim() == 3 and x.size(0) == 1:
             x = x[0]
@@ -218,3 +307,77 @@ class LSTM(torch.nn.Module):
         if s & _lib.BGCN_STATUS_SEQUENCE:
             raise IndexError("the batch holds a rootindex that does not increase strictly or is out of range, "
                              "a tree longer than max_len, or a label outside [0, out_feats)")
+
+
+def lstm_adam(model, lr: float = 5e-4, weight_decay: float = 1e-4) -> MultiAdam:
+    """The reference's optimiser (``LSTM_Twitter.py``: ``Adam(model.parameters(), lr, weight_decay)``)
+    as one :class:`MultiAdam` group over all ``4 num_layers + 2`` tensors: one launch per step."""
+    return MultiAdam([{"params": list(model.parameters())}], lr=lr, weight_decay=weight_decay)
+
+
+class LSTMTrainStep:
+    """The body of the reference's training loop (``LSTM_Twitter.py:96-126``) for a whole batch,
+    with no host sync besides ``max_len``'s: ``bgcn_lstm_train_grad`` (forward, loss, accuracy,
+    backward into buffers this object owns), then one :class:`MultiAdam` launch.  An invalid batch
+    is decided on the device: the call sets the optimiser's ``skip_flag``, the update writes nothing,
+    and :meth:`check_status` reports it with one read.  ``.grad`` is left alone."""
+
+    def __init__(self, model: LSTM, optimizer: MultiAdam = None, lr: float = 5e-4, weight_decay: float = 1e-4):
+        self.model = model
+        self.optimizer = lstm_adam(model, lr, weight_decay) if optimizer is None else optimizer
+        self.last_skipped = 0
+        self._st = None
+
+    def _state(self, dev):
+        st = self._st
+        if st is None or st["dev"] != dev:
+            by_name = dict(self.model.named_parameters())
+            st = {"dev": dev, "skip_count": torch.zeros(1, dtype=torch.int32, device=dev),
+                  "skip_flag": torch.zeros(1, dtype=torch.float32, device=dev),
+                  "grads": [torch.zeros(by_name[n].shape, dtype=torch.float32, device=dev)
+                            for n in self.model.names()]}
+            self._st = st
+        return st
+
+    @property
+    def step_count(self) -> int:
+        return self.optimizer.step_count
+
+    def grads(self):
+        """The last step's gradients by ``state_dict`` name (the step's own buffers, overwritten by the next)."""
+        return dict(zip(self.model.names(), self._st["grads"])) if self._st else {}
+
+    def step(self, data, pred: bool = False, max_len=None):
+        """One iteration; ``data`` as :meth:`LSTM.evaluate` takes it.  Returns ``(loss, correct)`` (0-dim
+        fp32 / int32 device tensors), plus ``pred`` ([B] int64) when ``pred=True``.  An invalid batch
+        skips the update on the device (``step_count`` still advances); :meth:`check_status` tells."""
+        m = self.model
+        x = m._batch_rows(data)
+        if not x.is_cuda:
+            raise _lib.BGCNError("bigcn_amd ops take device tensors (no CPU path)")
+        st = self._state(x.device)
+        r = m._train(x, data.rootindex, data.y, max_len, grads=st["grads"], want_pred=pred,
+                     skip_flag=st["skip_flag"])
+        by_id = {id(p): g for p, g in zip(m._tensors(), st["grads"])}
+        self.optimizer.step(grads=[by_id.get(id(p)) for p in self.optimizer.params()], skip_flag=st["skip_flag"],
+                            skip_count=st["skip_count"])
+        out = (r["loss"].view(()), r["correct"].view(()))
+        return out + (r["pred"],) if pred else out
+
+    def check_status(self) -> int:
+        """One host read: the number of updates skipped since the last check (also in
+        ``last_skipped``), after raising the ``IndexError`` of :meth:`LSTM.check_status` when a batch
+        stepped on since then was invalid."""
+        mst = self.model.__dict__.get("_state")
+        if self._st is None or mst is None:
+            self.last_skipped = 0
+            return 0
+        words = torch.cat([mst["seen"], self._st["skip_count"]]).tolist()   # the one read
+        mst["seen"].zero_()
+        self._st["skip_count"].zero_()
+        self.last_skipped = int(words[1])
+        raise_on_status(1 if int(words[0]) & _lib.BGCN_STATUS_SEQUENCE else 0,
+                        index_also=" (a rootindex that does not increase strictly, a tree longer than max_len, "
+                                   "or a label outside [0, out_feats))",
+                        suffix=f" ({self.last_skipped} updates skipped)")
+        return self.last_skipped

@@ -1198,6 +1198,61 @@ size_t bgcn_lstm_workspace_size(int64_t num_nodes, int64_t num_seqs, int64_t in_
                                 int64_t num_layers);
 int bgcn_lstm_eval(const bgcn_lstm_args* args, void* workspace, size_t workspace_bytes, bgcn_stream_t stream);
 
+/* --------------------------------------------------------------------------
+ * LSTM baseline, training: one iteration of model/Twitter/LSTM_Twitter.py:96-126 up to the
+ * optimiser - the forward of bgcn_lstm_eval, the mean NLL and the accuracy, and the gradient of
+ * the loss with respect to every parameter (and, optionally, x) - for a whole batch of trees as
+ * one launch sequence: no host round trip, no allocation.  Additive entry points:
+ * BGCN_ABI_VERSION is unchanged.
+ *
+ * `fwd` is bgcn_lstm_eval's argument struct with y required; logp, loss, correct, pred, h_n and
+ * out are bgcn_lstm_eval's bits on the same batch (the kernels are the same definitions; the
+ * training forward also keeps, per layer, the activated gates [N, 8 hid] over the input
+ * projections in place and the cell state of every row [N, 2 hid] in the workspace).
+ *
+ * Backward.  dz = (softmax - onehot(y)) / B per sequence; d_fc_w [C, 2 L hid] = dz^T h_n and
+ * d_fc_b = the column sums of dz, over the sequences in order; d h_n = dz fc_w enters dY_l at the
+ * sequence's last row (forward half) and first row (reverse half).  Per layer, from the last down,
+ * one launch per time step s = max_len - 1 .. 0 covers both directions and every sequence with
+ * s < len on the forward's row mapping: dh = dY_l[row] + W_hh^T dpre(step s + 1) (no recurrent
+ * term and no carry at s = len - 1), then with the saved i, f, g, o, c and c_prev (0 at s = 0)
+ *   dc = carry + dh o (1 - tanh^2 c)          dpre_o = dh tanh(c) o (1 - o)
+ *   dpre_i = dc g i (1 - i)   dpre_g = dc i (1 - g^2)   dpre_f = dc c_prev f (1 - f)   carry = dc f
+ * written over the row's gates.  After a layer's steps, with dG_l [N, 8 hid] those rows:
+ *   d_w_ih[l][d] = dG_l[:, d]^T X_l;   d_w_hh[l][d] = dG_l[:, d]^T Hprev_l[:, d], Hprev the layer's
+ *   output shifted by one row inside each sequence (forward: the previous row, reverse: the next
+ *   one, zero where the sequence has none);   dX_l = dG_l [w_ih[l][0] ; w_ih[l][1]], which is added
+ *   into dY_{l-1}, or written to dx [N, ldx] (in_feats columns; optional) for l = 0.
+ * The gradient buffers are written whole, never accumulated into.  Deterministic: no float
+ * atomics, every sum in a fixed order; two calls on the same inputs give the same bits.
+ *
+ * Rows of x before seq_start[0] belong to no sequence.  Their rows of dx are zeros, and they meet
+ * zero rows of dG_0 in d_w_ih[0]: they must hold finite numbers.
+ *
+ * Validity: as bgcn_lstm_eval (*status, BGCN_STATUS_SEQUENCE; a fault in seq_start or max_len
+ * empties every sequence, a bad label adds no loss and no gradient).  *skip_flag is 1.0f when
+ * *status is non-zero after the forward, else 0.0f: the optimiser's skip flag
+ * (bgcn_adam_multi_step, as bgcn_ebgcn_train_loss writes it).  A faulted batch reads and writes
+ * nothing out of bounds; its gradients are not to be used.
+ *
+ * BGCN_EINVAL before any HIP call: bgcn_lstm_eval's conditions, a null y / gradient pointer /
+ * skip_flag, a weight gradient or dx not 16-byte aligned, "workspace too small"
+ * (bgcn_lstm_train_workspace_size; 0 for an unsupported shape).
+ * -------------------------------------------------------------------------- */
+typedef struct bgcn_lstm_train_args {
+  bgcn_lstm_args fwd;            /* y required                               */
+  float* d_w_ih[4][2];           /* [layer][direction]: [4H, K_l]            */
+  float* d_w_hh[4][2];           /* [4H, H]                                  */
+  float* d_fc_w;                 /* [C, 2 L H]                               */
+  float* d_fc_b;                 /* [C]                                      */
+  float* dx;                     /* [N, ldx] (fwd.ldx), or NULL              */
+  float* skip_flag;              /* [1]                                      */
+} bgcn_lstm_train_args;
+size_t bgcn_lstm_train_workspace_size(int64_t num_nodes, int64_t num_seqs, int64_t in_feats, int64_t hid,
+                                      int64_t num_layers);
+int bgcn_lstm_train_grad(const bgcn_lstm_train_args* args, void* workspace, size_t workspace_bytes,
+                         bgcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
