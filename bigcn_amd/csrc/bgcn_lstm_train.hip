@@ -2,9 +2,9 @@
 // (model/Twitter/LSTM_Twitter.py:96-126: forward, mean NLL, accuracy, backward) for a whole batch
 // of trees as one launch sequence on the caller's stream, everything in the caller's workspace.
 //
-//   forward         bgcn_lstm_eval's launches (bgcn_lstm_body.h), the step as k_lstm_step<true>: per
-//                   layer the activated gates A_l [N, 8H] go over G in place and the cell states
-//                   into C_l [N, 2H]
+//   forward         lstm_forward (bgcn_lstm.hip) with save = true: bgcn_lstm_eval's launches, the
+//                   step as k_lstm_step<true>: per layer the activated gates A_l [N, 8H] go over G
+//                   in place and the cell states into C_l [N, 2H]
 //   k_lstm_bwd_setup   zero dY_{L-1}; zero the rows above seq_start[0] of every A_l and of Hprev
 //   k_lstm_head_bwd    per tree: dz = (softmax - onehot(y)) / B, d h_n = dz fc.weight
 //   k_lstm_fc_grad     d fc.weight = dz^T h_n, d fc.bias = column sums of dz (over b in order),
@@ -19,8 +19,8 @@
 //     dX_l = dG_l [W_ih_fwd ; W_ih_rev] (gemm_xw2) = dY_{l-1}, or the caller's dx
 //
 // Stream order is the only dependency between workgroups; no float atomics, every sum in a
-// fixed order.
-#include "bgcn_lstm_body.h"
+// fixed order.  This file holds the backward's kernels and launches only.
+#include "bgcn_lstm.h"
 
 namespace bgcn {
 namespace {
@@ -42,8 +42,7 @@ __global__ __launch_bounds__(256) void k_lstm_bwd_setup(BwdSetupArgs a) {
   const int64_t i0 = int64_t(blockIdx.x) * 256 + threadIdx.x, stride = int64_t(gridDim.x) * 256;
   const int64_t ny = a.N * 2 * a.H;
   for (int64_t i = i0; i < ny; i += stride) a.dYtop[i] = 0.f;
-  int64_t s0 = a.seq_start[0];
-  s0 = s0 < 0 ? 0 : (s0 > a.N ? a.N : s0);
+  const int64_t s0 = lstm_first_start(a.seq_start, a.N);
   const int64_t na = s0 * 8 * a.H, nh = s0 * 2 * a.H;
   for (int l = 0; l < a.L; ++l)
     for (int64_t i = i0; i < na; i += stride) a.A[l][i] = 0.f;
@@ -278,13 +277,8 @@ __global__ __launch_bounds__(256) void k_lstm_shift(ShiftArgs a) {
 }
 
 struct TrainWs {
-  float* A[kMaxLayers];   // [N, 8H]
-  float* Y[kMaxLayers];   // [N, 2H]
-  float* C[kMaxLayers];   // [N, 2H]
-  float *c, *dc;          // [2, B, H]
-  SeqInfo sq;
-  float* loss_row;
-  int32_t* predw;
+  LstmFwdWs f;            // the forward's share: G[l] holds A_l
+  float* dc;              // [2, B, H]
   float* dY[2];           // [N, 2H]: dY_l in dY[l & 1]
   float* Hprev;           // [N, 2H]
   float* WT;              // [2][H][4H]
@@ -293,19 +287,10 @@ struct TrainWs {
   size_t tn_bytes;
 };
 
-size_t carve_train(Carve& c, int64_t N, int64_t B, int64_t F, int64_t H, int64_t L, TrainWs* w) {
+size_t carve_train(Carve& c, int64_t N, int64_t B, int64_t F, int64_t H, int64_t L, float* out, TrainWs* w) {
   const size_t n = size_t(N), nb = size_t(B), h = size_t(H);
-  for (int l = 0; l < kMaxLayers; ++l) {
-    w->A[l] = l < L ? c.take<float>(n * 8 * h) : nullptr;
-    w->Y[l] = l < L ? c.take<float>(n * 2 * h) : nullptr;
-    w->C[l] = l < L ? c.take<float>(n * 2 * h) : nullptr;
-  }
-  w->c = c.take<float>(2 * nb * h);
+  carve_lstm_fwd(c, N, B, H, L, true, out, &w->f);
   w->dc = c.take<float>(2 * nb * h);
-  w->sq.start = c.take<int32_t>(nb);
-  w->sq.len = c.take<int32_t>(nb);
-  w->loss_row = c.take<float>(nb);
-  w->predw = c.take<int32_t>(nb);
   w->dY[0] = c.take<float>(n * 2 * h);
   w->dY[1] = c.take<float>(n * 2 * h);
   w->Hprev = c.take<float>(n * 2 * h);
@@ -325,61 +310,29 @@ size_t carve_train(Carve& c, int64_t N, int64_t B, int64_t F, int64_t H, int64_t
 int lstm_train_grad_impl(const bgcn_lstm_train_args* ta, void* ws, size_t ws_bytes, hipStream_t s) {
   BGCN_CHECK_ARG(ta, "null args");
   const bgcn_lstm_args* a = &ta->fwd;
+  BGCN_TRY(lstm_check_args(a, ws));
   const int64_t N = a->num_nodes, B = a->num_seqs, F = a->in_feats, H = a->hid, L = a->num_layers,
                 C = a->out_feats;
-  BGCN_CHECK_ARG(shape_ok(N, B, F, H, L), "unsupported shape (in_feats % 4, hid % 64 in [64, 1024], layers in [1, 4])");
-  BGCN_CHECK_ARG(C >= 1 && C <= kMaxOut, "out_feats must be in [1, 64]");
-  BGCN_CHECK_ARG(a->max_len >= 1, "max_len must be at least 1");
-  BGCN_CHECK_ARG(a->x && a->seq_start && a->fc_w && a->fc_b && a->logp && a->status && a->y && ta->d_fc_w &&
-                     ta->d_fc_b && ta->skip_flag,
-                 "null pointer");
-  BGCN_CHECK_ARG(a->ldx >= F && a->ldx % 4 == 0 && a16(a->x) && a16(ta->dx),
-                 "x and dx rows must be 16-byte aligned (ldx % 4)");
+  BGCN_CHECK_ARG(a->y && ta->d_fc_w && ta->d_fc_b && ta->skip_flag, "null pointer");
+  BGCN_CHECK_ARG(a16(ta->dx), "x and dx rows must be 16-byte aligned (ldx % 4)");
   for (int l = 0; l < L; ++l)
-    for (int d = 0; d < 2; ++d) {
-      BGCN_CHECK_ARG(a->w_ih[l][d] && a->w_hh[l][d] && a16(a->w_ih[l][d]) && a16(a->w_hh[l][d]),
-                     "null or unaligned LSTM weight");
+    for (int d = 0; d < 2; ++d)
       BGCN_CHECK_ARG(ta->d_w_ih[l][d] && ta->d_w_hh[l][d] && a16(ta->d_w_ih[l][d]) && a16(ta->d_w_hh[l][d]),
                      "null or unaligned LSTM weight gradient");
-    }
-  BGCN_CHECK_ARG(a16(a->fc_w) && a16(a->out) && a16(ws), "fc_w, out and the workspace must be 16-byte aligned");
   TrainWs w;
   Carve c(ws, ws_bytes);
-  carve_train(c, N, B, F, H, L, &w);
+  carve_train(c, N, B, F, H, L, a->out, &w);
   BGCN_CHECK_ARG(ws && c.ok(), "workspace too small");
-  if (a->out) w.Y[L - 1] = a->out;   // the last layer straight into the caller's [N, 2H]
   float* h_n = a->h_n ? a->h_n : w.h_n;
   const int D = int(2 * L * H);
-
-  // ---- forward: bgcn_lstm_eval's launches, the gates and cell states kept
-  SetupArgs su{a->seq_start, B, N, a->max_len, w.sq, {w.Y[0], w.Y[1], w.Y[2], w.Y[3]}, int(L), 2 * H, a->status};
-  hipLaunchKernelGGL(k_lstm_setup, dim3(64), dim3(256), 0, s, su);
-  BGCN_CHECK_LAUNCH();
   const int64_t steps = std::min<int64_t>(a->max_len, N);
-  const dim3 grid(unsigned(H / kUnits), 2, grid_for(B, kSeqTile));
-  for (int l = 0; l < L; ++l) {
-    const float* X = l == 0 ? a->x : w.Y[l - 1];
-    const int64_t K = l == 0 ? F : 2 * H, ldx = l == 0 ? a->ldx : 2 * H;
-    BGCN_TRY(gemm_xwt_impl(X, ldx, a->w_ih[l][0], a->w_ih[l][1], K, 4 * H, w.A[l], 8 * H, N, 8 * H, K, s, nullptr));
-    StepArgs st{w.A[l], {a->w_hh[l][0], a->w_hh[l][1]}, w.Y[l], w.c, w.sq, B, int(H), 0, w.C[l]};
-    for (int64_t k = 0; k < steps; ++k) {
-      st.s = int(k);
-      hipLaunchKernelGGL(k_lstm_step<true>, grid, dim3(256), 0, s, st);
-    }
-    BGCN_CHECK_LAUNCH();
-  }
-  LstmHeadArgs hd{{w.Y[0], w.Y[1], w.Y[2], w.Y[3]}, w.sq, B, int(H), int(L), int(C), a->fc_w, a->fc_b, a->y,
-                  a->logp, h_n, w.loss_row, w.predw, a->pred, a->status};
-  hipLaunchKernelGGL(k_lstm_head, dim3(unsigned(B)), dim3(256), 0, s, hd);
-  BGCN_CHECK_LAUNCH();
-  if (a->loss || a->correct) {
-    hipLaunchKernelGGL(k_lstm_finish, dim3(1), dim3(256), 0, s, w.loss_row, w.predw, a->y, B, a->loss, a->correct);
-    BGCN_CHECK_LAUNCH();
-  }
+  const LstmFwdWs& f = w.f;
+
+  BGCN_TRY(lstm_forward(a, f, true, h_n, s));   // the gates and cell states kept
 
   // ---- backward: the head
   const int top = int(L - 1);
-  BwdSetupArgs bs{a->seq_start, N, {w.A[0], w.A[1], w.A[2], w.A[3]}, int(L), H, w.Hprev, w.dY[top & 1]};
+  BwdSetupArgs bs{a->seq_start, N, {f.G[0], f.G[1], f.G[2], f.G[3]}, int(L), H, w.Hprev, w.dY[top & 1]};
   hipLaunchKernelGGL(k_lstm_bwd_setup, dim3(std::min<unsigned>(grid_for(N * 2 * H, 1024), 1024)), dim3(256), 0, s, bs);
   BGCN_CHECK_LAUNCH();
   HeadBwdArgs hb{a->logp, a->y, a->fc_w, B, int(C), D, w.dz, w.dhn};
@@ -395,30 +348,30 @@ int lstm_train_grad_impl(const bgcn_lstm_train_args* ta, void* ws, size_t ws_byt
                    unsigned(std::min<int64_t>(B, 65535)));
   for (int l = top; l >= 0; --l) {
     float* dY = w.dY[l & 1];
-    SeedArgs sd{dY, w.dhn, w.sq, int(H), D, l};
+    SeedArgs sd{dY, w.dhn, f.sq, int(H), D, l};
     hipLaunchKernelGGL(k_lstm_seed, dim3(unsigned(B)), dim3(256), 0, s, sd);
     WhhTArgs wt{{a->w_hh[l][0], a->w_hh[l][1]}, w.WT, int(H)};
     hipLaunchKernelGGL(k_lstm_whh_t, dim3(unsigned(H / 32), unsigned(4 * H / 32), 2), dim3(256), 0, s, wt);
     BGCN_CHECK_LAUNCH();
-    BwdStepArgs st{w.A[l], w.C[l], dY, w.WT, w.dc, w.sq, B, int(H), 0};
+    BwdStepArgs st{f.G[l], f.C[l], dY, w.WT, w.dc, f.sq, B, int(H), 0};
     for (int64_t k = steps - 1; k >= 0; --k) {
       st.s = int(k);
       hipLaunchKernelGGL(k_lstm_bwd_step, bgrid, dim3(256), 0, s, st);
     }
     BGCN_CHECK_LAUNCH();
-    const float* X = l == 0 ? a->x : w.Y[l - 1];
+    const float* X = l == 0 ? a->x : f.Y[l - 1];
     const int64_t K = l == 0 ? F : 2 * H, ldx = l == 0 ? a->ldx : 2 * H;
-    BGCN_TRY(gemm_tn_impl(w.A[l], 8 * H, X, ldx, ta->d_w_ih[l][0], ta->d_w_ih[l][1], K, 4 * H, 8 * H, K, N, w.tn,
+    BGCN_TRY(gemm_tn_impl(f.G[l], 8 * H, X, ldx, ta->d_w_ih[l][0], ta->d_w_ih[l][1], K, 4 * H, 8 * H, K, N, w.tn,
                           w.tn_bytes, s, -1, nullptr));
-    ShiftArgs sh{w.Y[l], w.Hprev, w.sq, B, int(H)};
+    ShiftArgs sh{f.Y[l], w.Hprev, f.sq, B, int(H)};
     hipLaunchKernelGGL(k_lstm_shift, sgrid, dim3(256), 0, s, sh);
     BGCN_CHECK_LAUNCH();
     for (int d = 0; d < 2; ++d)
-      BGCN_TRY(gemm_tn_impl(w.A[l] + d * 4 * H, 8 * H, w.Hprev + d * H, 2 * H, ta->d_w_hh[l][d], nullptr, H, 4 * H,
+      BGCN_TRY(gemm_tn_impl(f.G[l] + d * 4 * H, 8 * H, w.Hprev + d * H, 2 * H, ta->d_w_hh[l][d], nullptr, H, 4 * H,
                             4 * H, H, N, w.tn, w.tn_bytes, s, -1, nullptr));
     float* dX = l > 0 ? w.dY[(l - 1) & 1] : ta->dx;
     if (dX)
-      BGCN_TRY(gemm_xw2_impl(w.A[l], 8 * H, a->w_ih[l][0], a->w_ih[l][1], K, 4 * H, dX, l > 0 ? 2 * H : a->ldx, N, K,
+      BGCN_TRY(gemm_xw2_impl(f.G[l], 8 * H, a->w_ih[l][0], a->w_ih[l][1], K, 4 * H, dX, l > 0 ? 2 * H : a->ldx, N, K,
                              8 * H, s));
   }
   return BGCN_OK;
@@ -428,10 +381,10 @@ int lstm_train_grad_impl(const bgcn_lstm_train_args* ta, void* ws, size_t ws_byt
 
 extern "C" size_t bgcn_lstm_train_workspace_size(int64_t num_nodes, int64_t num_seqs, int64_t in_feats, int64_t hid,
                                                  int64_t num_layers) {
-  if (!bgcn::shape_ok(num_nodes, num_seqs, in_feats, hid, num_layers)) return 0;
+  if (!bgcn::lstm_shape_ok(num_nodes, num_seqs, in_feats, hid, num_layers)) return 0;
   bgcn::TrainWs w;
   bgcn::Carve c(nullptr, 0);
-  return bgcn::carve_train(c, num_nodes, num_seqs, in_feats, hid, num_layers, &w);
+  return bgcn::carve_train(c, num_nodes, num_seqs, in_feats, hid, num_layers, nullptr, &w);
 }
 
 extern "C" int bgcn_lstm_train_grad(const bgcn_lstm_train_args* args, void* workspace, size_t workspace_bytes,

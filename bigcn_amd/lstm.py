@@ -24,6 +24,12 @@ from . import _lib
 from ._lib import check, ptr, raise_on_status, stream_handle
 from .optim import MultiAdam
 
+# native entry point -> (the key of its workspace in the module's state, its workspace-size function)
+_ENTRY = {"bgcn_lstm_eval": ("ws", "bgcn_lstm_workspace_size"),
+          "bgcn_lstm_train_grad": ("tws", "bgcn_lstm_train_workspace_size")}
+# what sets BGCN_STATUS_SEQUENCE besides a bad rootindex: the end of both check_status messages
+_SEQUENCE_ALSO = "a tree longer than max_len, or a label outside [0, out_feats)"
+
 
 def max_sequence_len(rootindex, num_nodes: int) -> int:
     """The longest sequence of a batch whose tree ``b`` is the rows ``[rootindex[b], rootindex[b + 1])``
@@ -54,12 +60,14 @@ class LSTM(torch.nn.Module):
         self.version = version
 
     # ---- parameters
+    def names(self):
+        """The ``state_dict`` names in the order of the native call's tensors (:meth:`_tensors`)."""
+        return [f"lstm.{kind}_l{l}{rev}" for kind in ("weight_ih", "weight_hh") for l in range(self.num_layers)
+                for rev in ("", "_reverse")] + ["fc.weight", "fc.bias"]
+
     def _tensors(self):
-        out = []
-        for kind in ("weight_ih", "weight_hh"):
-            for l in range(self.num_layers):
-                out += [getattr(self.lstm, f"{kind}_l{l}"), getattr(self.lstm, f"{kind}_l{l}_reverse")]
-        return out + [self.fc.weight, self.fc.bias]
+        mods = {"lstm": self.lstm, "fc": self.fc}
+        return [getattr(mods[mod], attr) for mod, attr in (n.split(".") for n in self.names())]
 
     def _bind(self, dev):
         """The argument struct, refilled only when a parameter was rebound, moved or (a tensor the
@@ -83,7 +91,7 @@ class LSTM(torch.nn.Module):
         a.in_feats, a.hid, a.num_layers, a.out_feats = self.in_feats, self.hid_feats, L, self.out_feats
         if st is None or st["status"].device != dev:
             st = {"status": torch.zeros(1, dtype=torch.int32, device=dev),
-                  "seen": torch.zeros(1, dtype=torch.int32, device=dev), "ws": None, "sizes": None}
+                  "seen": torch.zeros(1, dtype=torch.int32, device=dev), "sizes": {}}
             self.__dict__["_state"] = st
         a.status = st["status"].data_ptr()
         st.update(key=key, args=a, held=held)
@@ -97,15 +105,32 @@ class LSTM(torch.nn.Module):
             return x.mean(dim=1)
         raise ValueError(f"pooling must be 'max' or 'mean', not {self.pooling!r}")
 
-    # ---- the native call
-    def _run(self, x, rootindex, max_len, y=None, logp=None, want_pred=False, want_states=False):
+    # ---- the native calls
+    def _workspace(self, st, entry, N, B, dev):
+        """The workspace of ``entry`` (:data:`_ENTRY`), kept in the module's state under the entry's key:
+        sized by the largest batch so far, asked for again only when ``(N, B)`` changes."""
+        key, size_fn = _ENTRY[entry]
+        if st["sizes"].get(key) != (N, B):
+            need = getattr(_lib.lib(), size_fn)(N, B, self.in_feats, self.hid_feats, self.num_layers)
+            if need == 0:
+                raise _lib.BGCNError(f"{entry}: unsupported shape (in_feats % 4, hid_feats % 64 in [64, 1024], "
+                                     "num_layers in [1, 4])")
+            if st.get(key) is None or st[key].numel() < need or st[key].device != dev:
+                st[key] = _lib.workspace(need, dev)
+            st["sizes"][key] = (N, B)
+        return st[key]
+
+    def _begin(self, entry, x, rootindex, max_len, y, logp=None, want_pred=False, want_states=False):
+        """What both native calls start with: the checks, ``x`` re-laid out where the kernels cannot read
+        it in place, ``rootindex`` and ``y`` on the device, the outputs, and the per-call fields of the
+        entry's ``LstmArgs``.  Returns ``(st, ws, r, (x, rootindex, y))``: ``r`` holds the outputs, and the
+        inputs as the kernels read them stay referenced by the caller until the call is queued."""
         if not x.is_cuda:
             raise _lib.BGCNError("bigcn_amd ops take device tensors (no CPU path)")
         if x.dim() != 2 or x.size(1) != self.in_feats:
             raise ValueError(f"the sequences' rows must be [N, {self.in_feats}], got {tuple(x.shape)}")
         dev = x.device
         st = self._bind(dev)
-        a = st["args"]
         if not (x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
                 and x.stride(0) >= x.size(1)):
             x = x.float().contiguous()
@@ -117,102 +142,60 @@ class LSTM(torch.nn.Module):
             y = y.to(device=dev, dtype=torch.int64).contiguous()
             if y.numel() != B:
                 raise ValueError("y must have one label per tree")
+        if max_len is None:
+            max_len = max_sequence_len(rootindex, N)
         if logp is None:
             logp = torch.empty(B, C, dtype=torch.float32, device=dev)
         elif logp.dtype != torch.float32 or not logp.is_contiguous() or logp.numel() != B * C or logp.device != dev:
             raise ValueError("logp must be a contiguous fp32 [B, out_feats] tensor")
-        lib = _lib.lib()
-        sizes = (N, B)
-        if st["sizes"] != sizes:
-            need = lib.bgcn_lstm_workspace_size(N, B, self.in_feats, H, L)
-            if need == 0:
-                raise _lib.BGCNError("bgcn_lstm_eval: unsupported shape (in_feats % 4, hid_feats % 64 in [64, 1024], "
-                                     "num_layers in [1, 4])")
-            if st["ws"] is None or st["ws"].numel() < need or st["ws"].device != dev:
-                st["ws"] = _lib.workspace(need, dev)
-            st["sizes"] = sizes
-        ws = st["ws"]
-        loss = torch.empty(1, dtype=torch.float32, device=dev) if y is not None else None
-        correct = torch.empty(1, dtype=torch.int32, device=dev) if y is not None else None
-        pred = torch.empty(B, dtype=torch.int64, device=dev) if want_pred else None
-        out = torch.empty(N, 2 * H, dtype=torch.float32, device=dev) if want_states else None
-        h_n = torch.empty(2 * L, B, H, dtype=torch.float32, device=dev) if want_states else None
+        ws = self._workspace(st, entry, N, B, dev)
+        r = {"logp": logp,
+             "loss": torch.empty(1, dtype=torch.float32, device=dev) if y is not None else None,
+             "correct": torch.empty(1, dtype=torch.int32, device=dev) if y is not None else None,
+             "pred": torch.empty(B, dtype=torch.int64, device=dev) if want_pred else None,
+             "out": torch.empty(N, 2 * H, dtype=torch.float32, device=dev) if want_states else None,
+             "h_n": torch.empty(2 * L, B, H, dtype=torch.float32, device=dev) if want_states else None}
+        a = st["args"] if entry == "bgcn_lstm_eval" else self._train_args(st)
         a.x, a.ldx, a.num_nodes = x.data_ptr(), x.stride(0), N
         a.seq_start, a.num_seqs, a.max_len = rootindex.data_ptr(), B, int(max_len)
-        a.y, a.logp, a.h_n, a.out = ptr(y), logp.data_ptr(), ptr(h_n), ptr(out)
-        a.loss, a.correct, a.pred = ptr(loss), ptr(correct), ptr(pred)
-        check(lib.bgcn_lstm_eval(ctypes.addressof(a), ptr(ws), ws.numel(), stream_handle()))
+        a.y, a.logp, a.h_n, a.out = ptr(y), logp.data_ptr(), ptr(r["h_n"]), ptr(r["out"])
+        a.loss, a.correct, a.pred = ptr(r["loss"]), ptr(r["correct"]), ptr(r["pred"])
+        return st, ws, r, (x, rootindex, y)
+
+    def _run(self, x, rootindex, max_len, y=None, logp=None, want_pred=False, want_states=False):
+        st, ws, r, inputs = self._begin("bgcn_lstm_eval", x, rootindex, max_len, y, logp, want_pred, want_states)
+        check(_lib.lib().bgcn_lstm_eval(ctypes.addressof(st["args"]), ptr(ws), ws.numel(), stream_handle()))
         st["seen"].bitwise_or_(st["status"])   # the call zeroes its status word; check_status reads this one
-        return {"logp": logp, "loss": loss, "correct": correct, "pred": pred, "out": out, "h_n": h_n}
+        return r
 
-    def names(self):
-        """The ``state_dict`` names in the order of the native call's tensors (:meth:`_tensors`)."""
-        out = []
-        for kind in ("weight_ih", "weight_hh"):
-            for l in range(self.num_layers):
-                out += [f"lstm.{kind}_l{l}", f"lstm.{kind}_l{l}_reverse"]
-        return out + ["fc.weight", "fc.bias"]
-
-    def _train(self, x, rootindex, y, max_len, dx=False, grads=None, want_pred=False, skip_flag=None):
-        """One ``bgcn_lstm_train_grad`` call.  ``grads``: fp32 contiguous buffers in :meth:`names`
-        order (default: new ones)."""
-        if not x.is_cuda:
-            raise _lib.BGCNError("bigcn_amd ops take device tensors (no CPU path)")
-        if x.dim() != 2 or x.size(1) != self.in_feats:
-            raise ValueError(f"the sequences' rows must be [N, {self.in_feats}], got {tuple(x.shape)}")
-        dev = x.device
-        st = self._bind(dev)
-        if not (x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
-                and x.stride(0) >= x.size(1)):
-            x = x.float().contiguous()
-        rootindex = rootindex.to(device=dev, dtype=torch.int64).contiguous()
-        N, B, H, L, C = int(x.size(0)), int(rootindex.numel()), self.hid_feats, self.num_layers, self.out_feats
-        if N < 1 or B < 1:
-            raise ValueError("the batch needs at least one row and one tree")
-        y = y.to(device=dev, dtype=torch.int64).contiguous()
-        if y.numel() != B:
-            raise ValueError("y must have one label per tree")
-        if max_len is None:
-            max_len = max_sequence_len(rootindex, N)
-        lib = _lib.lib()
-        sizes = (N, B)
-        if st.get("tsizes") != sizes:
-            need = lib.bgcn_lstm_train_workspace_size(N, B, self.in_feats, H, L)
-            if need == 0:
-                raise _lib.BGCNError("bgcn_lstm_train_grad: unsupported shape (in_feats % 4, hid_feats % 64 in "
-                                     "[64, 1024], num_layers in [1, 4])")
-            if st.get("tws") is None or st["tws"].numel() < need or st["tws"].device != dev:
-                st["tws"] = _lib.workspace(need, dev)
-            st["tsizes"] = sizes
-        ws = st["tws"]
-        if grads is None:
-            grads = [torch.empty(t.shape, dtype=torch.float32, device=dev) for t in st["held"]]
-        if skip_flag is None:
-            skip_flag = torch.empty(1, dtype=torch.float32, device=dev)
-        logp = torch.empty(B, C, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
-        correct = torch.empty(1, dtype=torch.int32, device=dev)
-        pred = torch.empty(B, dtype=torch.int64, device=dev) if want_pred else None
-        gx = torch.empty(N, x.stride(0), dtype=torch.float32, device=dev) if dx else None
+    def _train_args(self, st):
+        """The module's ``LstmTrainArgs``, its forward half a fresh copy of the bound ``LstmArgs``."""
         ta = st.get("targs")
         if ta is None:
             ta = st["targs"] = _lib.LstmTrainArgs()
         ctypes.memmove(ctypes.addressof(ta.fwd), ctypes.addressof(st["args"]), ctypes.sizeof(_lib.LstmArgs))
-        a = ta.fwd
-        a.x, a.ldx, a.num_nodes = x.data_ptr(), x.stride(0), N
-        a.seq_start, a.num_seqs, a.max_len = rootindex.data_ptr(), B, int(max_len)
-        a.y, a.logp, a.h_n, a.out = y.data_ptr(), logp.data_ptr(), None, None
-        a.loss, a.correct, a.pred = loss.data_ptr(), correct.data_ptr(), ptr(pred)
+        return ta.fwd
+
+    def _train(self, x, rootindex, y, max_len, dx=False, grads=None, want_pred=False, skip_flag=None):
+        """One ``bgcn_lstm_train_grad`` call.  ``grads``: fp32 contiguous buffers in :meth:`names`
+        order (default: new ones)."""
+        st, ws, r, inputs = self._begin("bgcn_lstm_train_grad", x, rootindex, max_len, y, want_pred=want_pred)
+        x, dev, L, ta = inputs[0], x.device, self.num_layers, st["targs"]
+        if grads is None:
+            grads = [torch.empty(t.shape, dtype=torch.float32, device=dev) for t in st["held"]]
+        if skip_flag is None:
+            skip_flag = torch.empty(1, dtype=torch.float32, device=dev)
+        gx = torch.empty(x.size(0), x.stride(0), dtype=torch.float32, device=dev) if dx else None
         for l in range(L):
             for d in range(2):
                 ta.d_w_ih[l][d] = grads[2 * l + d].data_ptr()
                 ta.d_w_hh[l][d] = grads[2 * L + 2 * l + d].data_ptr()
         ta.d_fc_w, ta.d_fc_b = grads[4 * L].data_ptr(), grads[4 * L + 1].data_ptr()
         ta.dx, ta.skip_flag = ptr(gx), skip_flag.data_ptr()
-        check(lib.bgcn_lstm_train_grad(ctypes.addressof(ta), ptr(ws), ws.numel(), stream_handle()))
+        check(_lib.lib().bgcn_lstm_train_grad(ctypes.addressof(ta), ptr(ws), ws.numel(), stream_handle()))
         st["seen"].bitwise_or_(st["status"])
-        return {"logp": logp, "loss": loss, "correct": correct, "pred": pred, "grads": grads,
-                "dx": None if gx is None else gx[:, :self.in_feats], "skip_flag": skip_flag}
+        r.update(grads=grads, dx=None if gx is None else gx[:, :self.in_feats], skip_flag=skip_flag)
+        return r
 
     def grad_batch(self, x, rootindex, y, max_len=None, dx=False):
         """Forward, mean NLL loss and backward of one batch of trees (``LSTM_Twitter.py:96-124`` up to
@@ -306,7 +289,7 @@ class LSTM(torch.nn.Module):
         st["seen"].zero_()
         if s & _lib.BGCN_STATUS_SEQUENCE:
             raise IndexError("the batch holds a rootindex that does not increase strictly or is out of range, "
-                             "a tree longer than max_len, or a label outside [0, out_feats)")
+                             + _SEQUENCE_ALSO)
 
 
 def lstm_adam(model, lr: float = 5e-4, weight_decay: float = 1e-4) -> MultiAdam:
@@ -377,7 +360,6 @@ class LSTMTrainStep:
         self._st["skip_count"].zero_()
         self.last_skipped = int(words[1])
         raise_on_status(1 if int(words[0]) & _lib.BGCN_STATUS_SEQUENCE else 0,
-                        index_also=" (a rootindex that does not increase strictly, a tree longer than max_len, "
-                                   "or a label outside [0, out_feats))",
+                        index_also=f" (a rootindex that does not increase strictly, {_SEQUENCE_ALSO})",
                         suffix=f" ({self.last_skipped} updates skipped)")
         return self.last_skipped

@@ -16,10 +16,10 @@ import torch
 import torch.nn.functional as F
 
 import lstm_ref as R
+from lstm_gpu_util import DEV, _data, _new_model, _x
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 TOL = 1e-4
 SEQ_TILE = 32   # sequences per workgroup of a step launch (BGCN_LSTM_SEQ_TILE): "tile_plus_one" has 33
 _parity = {}
@@ -27,23 +27,7 @@ _parity = {}
 
 @functools.lru_cache(maxsize=None)
 def _model(name, version=2, pooling='max'):
-    from bigcn_amd import LSTM
-    c = R.case(name)
-    m = LSTM(c.cfg["in_feats"], c.cfg["hid"], c.cfg["out"], c.cfg["layers"], version=version, pooling=pooling)
-    m.load_state_dict({k: v.float() for k, v in c.sd.items()}, strict=True)
-    return m.to(DEV).eval()
-
-
-def _x(c):
-    """The case's rows on the device, with the case's own row stride (a column slice for pad_cols)."""
-    wide = torch.empty(c.N, c.x.stride(0), dtype=torch.float32, device=DEV)
-    x = wide[:, :c.cfg["in_feats"]]
-    x.copy_(c.x)
-    return x
-
-
-def _data(c):
-    return SimpleNamespace(cls=_x(c), rootindex=c.rootindex.to(DEV), y=c.y.to(DEV))
+    return _new_model(R.case(name), version=version, pooling=pooling)
 
 
 def _err(got, want):

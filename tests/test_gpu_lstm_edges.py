@@ -30,10 +30,11 @@ import torch
 import torch.nn.functional as F
 
 import lstm_ref as R
+import lstm_gpu_util as U
+from lstm_gpu_util import DEV, _buf, _data, _ends, _x
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 TOL = 1e-4
 _parity = {}
 
@@ -43,11 +44,7 @@ def _case(name):
 
 
 def _new_model(name, sd=None):
-    from bigcn_amd import LSTM
-    c = _case(name)
-    m = LSTM(c.cfg["in_feats"], c.cfg["hid"], c.cfg["out"], c.cfg["layers"], version=2)
-    m.load_state_dict({k: v.float() for k, v in (sd or c.sd).items()}, strict=True)
-    return m.to(DEV).eval()
+    return U._new_model(_case(name), sd)
 
 
 @functools.lru_cache(maxsize=None)
@@ -55,22 +52,8 @@ def _model(name):
     return _new_model(name)
 
 
-def _x(c):
-    return c.x.float().contiguous().to(DEV)
-
-
-def _data(c, rootindex=None, y=None):
-    return SimpleNamespace(cls=_x(c), rootindex=(c.rootindex if rootindex is None else rootindex).to(DEV),
-                           y=(c.y if y is None else y).to(DEV))
-
-
 def _err(got, want):
     return float((got.double().cpu() - want).abs().max())
-
-
-def _ends(c, rootindex=None):
-    roots = (c.rootindex if rootindex is None else rootindex).tolist()
-    return list(zip(roots, roots[1:] + [c.N]))
 
 
 # ---------------------------------------------------------------- a. parity
@@ -149,24 +132,6 @@ def test_argmax_takes_the_first_of_two_equal_classes():
 
 
 # ---------------------------------------------------------------- the C ABI, called directly
-@functools.lru_cache(maxsize=None)
-def _weights(name):
-    return {k: v.float().contiguous().to(DEV) for k, v in _case(name).sd.items()}
-
-
-def _buf(nbytes, fill):
-    """A device buffer of at least ``nbytes`` holding zero bytes, 0xFF bytes (NaN as fp32) or the fp32 3.0e38."""
-    b = torch.empty((max(int(nbytes), 16) + 15) // 16 * 16, dtype=torch.uint8, device=DEV)
-    if fill == "zero":
-        b.zero_()
-    elif fill == "ff":
-        b.fill_(0xFF)
-    else:
-        assert fill == "big"
-        b.view(torch.float32).fill_(3.0e38)
-    return b
-
-
 OUTPUTS = ("out", "h_n", "loss", "correct", "pred")
 
 
@@ -177,7 +142,7 @@ def _capi(name, fill="zero", want=OUTPUTS, labels=True, rootindex=None, max_len=
     from bigcn_amd import _lib
     lib = _lib.lib()
     c = _case(name)
-    w = _weights(name)
+    w = U._weights(name, _case)
     H, L, C, N, B = c.cfg["hid"], c.cfg["layers"], c.cfg["out"], c.N, c.B
     x = _x(c)
     root = (c.rootindex if rootindex is None else rootindex).to(DEV)
@@ -189,15 +154,7 @@ def _capi(name, fill="zero", want=OUTPUTS, labels=True, rootindex=None, max_len=
             "h_n": _buf(4 * 2 * L * B * H, fill), "loss": _buf(4, fill), "correct": _buf(4, fill),
             "pred": _buf(8 * B, fill)}
     a = _lib.LstmArgs()
-    a.x, a.ldx, a.num_nodes, a.in_feats, a.hid, a.num_layers, a.out_feats = x.data_ptr(), x.stride(0), N, \
-        c.cfg["in_feats"], H, L, C
-    a.seq_start, a.num_seqs, a.max_len = root.data_ptr(), B, c.max_len if max_len is None else max_len
-    for l in range(L):
-        for d in range(2):
-            rev = "_reverse" if d else ""
-            a.w_ih[l][d] = w[f"lstm.weight_ih_l{l}{rev}"].data_ptr()
-            a.w_hh[l][d] = w[f"lstm.weight_hh_l{l}{rev}"].data_ptr()
-    a.fc_w, a.fc_b = w["fc.weight"].data_ptr(), w["fc.bias"].data_ptr()
+    U._fwd_args(a, c, w, x, root, max_len)
     a.y = y.data_ptr() if labels else None
     a.logp, a.status = bufs["logp"].data_ptr(), bufs["status"].data_ptr()
     for k in OUTPUTS:

@@ -21,44 +21,21 @@ import torch.nn.functional as F
 
 import lstm_ref as R
 import lstm_train_ref as T
+import lstm_gpu_util as U
+from lstm_gpu_util import DEV, _buf, _data, _ends, _x
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 _parity = {}
 
 
 def _new_model(c, train=True):
-    from bigcn_amd import LSTM
-    m = LSTM(c.cfg["in_feats"], c.cfg["hid"], c.cfg["out"], c.cfg["layers"], version=2)
-    m.load_state_dict({k: v.float() for k, v in c.sd.items()}, strict=True)
-    m = m.to(DEV)
-    return m.train() if train else m.eval()
+    return U._new_model(c, train=train)
 
 
 @functools.lru_cache(maxsize=None)
 def _model(name):
     return _new_model(T.case(name))
-
-
-def _x(c):
-    """The case's rows on the device; with pad_cols a column slice of a wider tensor (ldx > in_feats)."""
-    pad = c.cfg.get("pad_cols", 0)
-    if not pad:
-        return c.x.float().contiguous().to(DEV)
-    wide = torch.full((c.N, c.cfg["in_feats"] + pad), 7.0, device=DEV)
-    wide[:, :c.cfg["in_feats"]] = c.x.float().to(DEV)
-    return wide[:, :c.cfg["in_feats"]]
-
-
-def _data(c, rootindex=None, y=None):
-    return SimpleNamespace(cls=_x(c), rootindex=(c.rootindex if rootindex is None else rootindex).to(DEV),
-                           y=(c.y if y is None else y).to(DEV))
-
-
-def _ends(c, rootindex=None):
-    roots = (c.rootindex if rootindex is None else rootindex).tolist()
-    return list(zip(roots, roots[1:] + [c.N]))
 
 
 def _same_grads(got, want):
@@ -103,30 +80,42 @@ def test_gradients_match_the_fp64_autograd_loop(name):
 
 
 # ---------------------------------------------------------------- the C ABI, called directly
-@functools.lru_cache(maxsize=None)
-def _weights(name):
-    return {k: v.float().contiguous().to(DEV) for k, v in T.case(name).sd.items()}
+def _states(c, bufs):
+    """Host copies of the caller's ``out [N, 2H]`` and ``h_n [2L, B, H]``."""
+    H, L = c.cfg["hid"], c.cfg["layers"]
+    return (bufs["out"].view(torch.float32)[:c.N * 2 * H].view(c.N, 2 * H).cpu(),
+            bufs["h_n"].view(torch.float32)[:2 * L * c.B * H].view(2 * L, c.B, H).cpu())
 
 
-def _buf(nbytes, fill):
-    b = torch.empty((max(int(nbytes), 16) + 15) // 16 * 16, dtype=torch.uint8, device=DEV)
-    if fill == "zero":
-        b.zero_()
-    elif fill == "ff":
-        b.fill_(0xFF)
-    else:
-        assert fill == "big"
-        b.view(torch.float32).fill_(3.0e38)
-    return b
-
-
-def _capi(name, fill="zero", rootindex=None, y=None, max_len=None):
-    """One bgcn_lstm_train_grad call on a workspace, outputs and gradient buffers all pre-filled with
-    ``fill``.  Returns host copies of every output, the status word and the skip flag."""
+def _eval_states(name):
+    """``(out, h_n)`` of one bgcn_lstm_eval call on the case, both pre-filled with 0xFF bytes."""
     from bigcn_amd import _lib
     lib = _lib.lib()
     c = T.case(name)
-    w = _weights(name)
+    H, L = c.cfg["hid"], c.cfg["layers"]
+    x, root, y = _x(c), c.rootindex.to(DEV), c.y.to(DEV)
+    ws = _buf(lib.bgcn_lstm_workspace_size(c.N, c.B, c.cfg["in_feats"], H, L), "ff")
+    bufs = {"logp": _buf(4 * c.B * c.cfg["out"], "ff"), "status": _buf(4, "ff"),
+            "out": _buf(4 * c.N * 2 * H, "ff"), "h_n": _buf(4 * 2 * L * c.B * H, "ff")}
+    a = _lib.LstmArgs()
+    U._fwd_args(a, c, U._weights(name, T.case), x, root)
+    a.y, a.logp, a.status = y.data_ptr(), bufs["logp"].data_ptr(), bufs["status"].data_ptr()
+    a.out, a.h_n = bufs["out"].data_ptr(), bufs["h_n"].data_ptr()
+    rc = lib.bgcn_lstm_eval(ctypes.addressof(a), ws.data_ptr(), ws.numel(), _lib.stream_handle())
+    assert rc == 0, lib.bgcn_last_error()
+    torch.cuda.synchronize()
+    assert int(bufs["status"].view(torch.int32)[0]) == 0
+    return _states(c, bufs)
+
+
+def _capi(name, fill="zero", rootindex=None, y=None, max_len=None, states=False):
+    """One bgcn_lstm_train_grad call on a workspace, outputs and gradient buffers all pre-filled with
+    ``fill``.  Returns host copies of every output, the status word and the skip flag.  ``states``: the
+    call also gets the caller's ``out`` and ``h_n`` (else NULL)."""
+    from bigcn_amd import _lib
+    lib = _lib.lib()
+    c = T.case(name)
+    w = U._weights(name, T.case)
     H, L, C, N, B, Fin = c.cfg["hid"], c.cfg["layers"], c.cfg["out"], c.N, c.B, c.cfg["in_feats"]
     x = _x(c)
     root = (c.rootindex if rootindex is None else rootindex).to(DEV)
@@ -141,17 +130,16 @@ def _capi(name, fill="zero", rootindex=None, y=None, max_len=None):
         bufs[k] = _buf(4 * int(torch.tensor(shp).prod()), fill)
     t = _lib.LstmTrainArgs()
     a = t.fwd
-    a.x, a.ldx, a.num_nodes, a.in_feats, a.hid, a.num_layers, a.out_feats = x.data_ptr(), x.stride(0), N, Fin, H, L, C
-    a.seq_start, a.num_seqs, a.max_len = root.data_ptr(), B, c.max_len if max_len is None else max_len
+    U._fwd_args(a, c, w, x, root, max_len)
     for l in range(L):
         for d in range(2):
             rev = "_reverse" if d else ""
-            a.w_ih[l][d] = w[f"lstm.weight_ih_l{l}{rev}"].data_ptr()
-            a.w_hh[l][d] = w[f"lstm.weight_hh_l{l}{rev}"].data_ptr()
             t.d_w_ih[l][d] = bufs[f"lstm.weight_ih_l{l}{rev}"].data_ptr()
             t.d_w_hh[l][d] = bufs[f"lstm.weight_hh_l{l}{rev}"].data_ptr()
-    a.fc_w, a.fc_b, a.y = w["fc.weight"].data_ptr(), w["fc.bias"].data_ptr(), yy.data_ptr()
-    a.logp, a.status = bufs["logp"].data_ptr(), bufs["status"].data_ptr()
+    a.y, a.logp, a.status = yy.data_ptr(), bufs["logp"].data_ptr(), bufs["status"].data_ptr()
+    if states:
+        bufs.update(out=_buf(4 * N * 2 * H, fill), h_n=_buf(4 * 2 * L * B * H, fill))
+        a.out, a.h_n = bufs["out"].data_ptr(), bufs["h_n"].data_ptr()
     a.loss, a.correct, a.pred = bufs["loss"].data_ptr(), bufs["correct"].data_ptr(), bufs["pred"].data_ptr()
     t.d_fc_w, t.d_fc_b = bufs["fc.weight"].data_ptr(), bufs["fc.bias"].data_ptr()
     t.dx, t.skip_flag = bufs["x"].data_ptr(), bufs["skip_flag"].data_ptr()
@@ -168,6 +156,8 @@ def _capi(name, fill="zero", rootindex=None, y=None, max_len=None):
         n = int(torch.tensor(shp).prod())
         r.grads[k] = bufs[k].view(torch.float32)[:n].view(shp).cpu()
     r.grads["x"] = bufs["x"].view(torch.float32)[:N * x.stride(0)].view(N, x.stride(0))[:, :Fin].cpu()
+    if states:
+        r.out, r.h_n = _states(c, bufs)
     return r
 
 
@@ -184,7 +174,10 @@ def _full(name):
 # ---------------------------------------------------------------- held bit for bit
 @pytest.mark.parametrize("name", ["boundaries", "three_layers", "offset_strided", "t_many_trees"])
 def test_the_training_forward_has_the_bits_of_evaluate(name):
-    """One definition of the step, the head and the final reduction serves both entry points."""
+    """One forward (lstm_forward and its kernels) serves both entry points.  include/bgcn.h also
+    promises bgcn_lstm_eval's bits in the training call's optional ``out`` and ``h_n``: with ``out`` the
+    last layer's output lives in the caller's buffer, which the backward then reads, so the gradients of
+    that call must be the bits of the call without it."""
     c = T.case(name)
     r = _full(name)
     m = _new_model(c, train=False)
@@ -198,6 +191,14 @@ def test_the_training_forward_has_the_bits_of_evaluate(name):
     # and through the module
     loss2, correct2, _ = _model(name).grad_batch(_x(c), c.rootindex.to(DEV), c.y.to(DEV), max_len=c.max_len)
     assert torch.equal(loss2, loss) and torch.equal(correct2, correct)
+    # the caller's out and h_n, pre-filled with 0xFF bytes
+    got = _capi(name, "ff", states=True)
+    out, h_n = _eval_states(name)
+    assert got.status == 0 and got.skip_flag == 0.0
+    assert torch.equal(got.out, out) and torch.equal(got.h_n, h_n)
+    first = int(c.rootindex[0])
+    assert float(got.out[:first].abs().sum()) == 0.0   # offset_strided: the rows above the first tree
+    _same_grads(got.grads, r.grads)
 
 
 @pytest.mark.parametrize("name", ["boundaries", "t_rows_over_switch"])

@@ -76,7 +76,8 @@ def timed(fn, warmup, iters):
     return float(np.median(ts)), float(np.min(ts))
 
 
-def run(name, cfg, B, seed, warmup, iters, ref_iters):
+def batch(cfg, B, seed):
+    """The seeded batch and model of one shape: ``(data, N, max_len, model)``, the model in eval mode."""
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(seed)
     sizes = synth_tree_sizes(rng, B, 64)
@@ -88,7 +89,12 @@ def run(name, cfg, B, seed, warmup, iters, ref_iters):
     data = SimpleNamespace(cls=cls.to(dev), rootindex=root_cpu.to(dev),
                            y=torch.randint(0, cfg[2], (B,), generator=g).to(dev))
     torch.manual_seed(seed)
-    model = LSTM(*cfg, version=2).to(dev).eval()
+    return data, N, max_len, LSTM(*cfg, version=2).to(dev).eval()
+
+
+def run(name, cfg, B, seed, warmup, iters, ref_iters):
+    data, N, max_len, model = batch(cfg, B, seed)
+    dev = data.cls.device
     logp = torch.empty(B, cfg[2], device=dev)
     ours = timed(lambda: model.evaluate(data, logp=logp, max_len=max_len), warmup, iters)
     model.check_status()
@@ -105,18 +111,9 @@ def run(name, cfg, B, seed, warmup, iters, ref_iters):
 
 
 def run_train(name, cfg, B, seed, warmup, iters, ref_iters):
-    dev = torch.device("cuda:0")
-    rng = np.random.default_rng(seed)
-    sizes = synth_tree_sizes(rng, B, 64)
-    N = int(sizes.sum())
-    g = torch.Generator().manual_seed(seed)
-    cls = torch.randn(N, cfg[0], generator=g)
-    root_cpu = torch.tensor(np.concatenate(([0], np.cumsum(sizes)[:-1])), dtype=torch.int64)
-    max_len = max_sequence_len(root_cpu, N)
-    data = SimpleNamespace(cls=cls.to(dev), rootindex=root_cpu.to(dev),
-                           y=torch.randint(0, cfg[2], (B,), generator=g).to(dev))
-    torch.manual_seed(seed)
-    model = LSTM(*cfg, version=2).to(dev).train()
+    data, N, max_len, model = batch(cfg, B, seed)
+    dev = data.cls.device
+    model.train()
     sd = {k: v.clone() for k, v in model.state_dict().items()}
     step = LSTMTrainStep(model)
     first = float(step.step(data, max_len=max_len)[0])        # the first loss, on the initial weights
