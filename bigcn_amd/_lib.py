@@ -44,6 +44,8 @@ BGCN_STATUS_BATCH_UNSORTED = 128   # bgcn_ebgcn_eval_step: the batch vector is n
 BGCN_STATUS_SEQUENCE = 256   # bgcn_lstm_eval: a bad sequence start, a sequence over max_len, a bad label
 BGCN_LSTM_SEQ_TILE = 32   # sequences per workgroup of a step launch of bgcn_lstm_eval
 BGCN_LSTM_MAX_LAYERS = 4
+BGCN_BERT_MAX_LAYERS = 24
+BGCN_BERT_QUERY_TILE = 32   # queries per workgroup of bgcn_bert_eval's attention kernel
 
 # every symbol include/bgcn.h declares (checked by tests/test_capi.py)
 EXPORTED_SYMBOLS = (
@@ -73,6 +75,7 @@ EXPORTED_SYMBOLS = (
     "bgcn_ebgcn_conv2_lin_train_workspace_size", "bgcn_ebgcn_conv2_lin_train_fwd", "bgcn_ebgcn_conv2_lin_train_bwd",
     "bgcn_adam_multi_table_size", "bgcn_adam_multi_plan", "bgcn_adam_multi_step", "bgcn_ebgcn_train_loss",
     "bgcn_lstm_workspace_size", "bgcn_lstm_eval", "bgcn_lstm_train_workspace_size", "bgcn_lstm_train_grad",
+    "bgcn_bert_workspace_size", "bgcn_bert_eval",
 )
 
 BGCN_ADAM_MULTI_MAX_TENSORS = 128
@@ -215,6 +218,26 @@ class LstmTrainArgs(Structure):
         ("fwd", LstmArgs),
         ("d_w_ih", (c_void_p * 2) * BGCN_LSTM_MAX_LAYERS), ("d_w_hh", (c_void_p * 2) * BGCN_LSTM_MAX_LAYERS),
         ("d_fc_w", c_void_p), ("d_fc_b", c_void_p), ("dx", c_void_p), ("skip_flag", c_void_p),
+    ]
+
+
+class BertLayer(Structure):
+    """bgcn_bert_layer (include/bgcn.h): one encoder layer's weights, in the header's order."""
+    _fields_ = [(n, c_void_p) for n in ("q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "ao_w", "ao_b", "ao_ln_w", "ao_ln_b",
+                                        "i_w", "i_b", "o_w", "o_b", "o_ln_w", "o_ln_b")]
+
+
+class BertArgs(Structure):
+    """bgcn_bert_args (include/bgcn.h)."""
+    _fields_ = [
+        ("x", c_void_p), ("ldx", c_int64), ("num_nodes", c_int64), ("seq_start", c_void_p), ("num_seqs", c_int64),
+        ("hidden", c_int64), ("heads", c_int64), ("intermediate", c_int64), ("num_layers", c_int64),
+        ("max_pos", c_int64), ("out_feats", c_int64), ("ln_eps", c_float), ("reserved", c_int32),
+        ("pos_emb", c_void_p), ("type_emb", c_void_p), ("emb_ln_w", c_void_p), ("emb_ln_b", c_void_p),
+        ("layer", BertLayer * BGCN_BERT_MAX_LAYERS),
+        ("pooler_w", c_void_p), ("pooler_b", c_void_p), ("fc_w", c_void_p), ("fc_b", c_void_p), ("y", c_void_p),
+        ("logp", c_void_p), ("loss", c_void_p), ("correct", c_void_p), ("pred", c_void_p),
+        ("hidden_out", c_void_p), ("hidden_sum", c_void_p), ("attn_sum", c_void_p), ("status", c_void_p),
     ]
 
 
@@ -387,6 +410,8 @@ _SIGS = {
     "bgcn_lstm_eval": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_lstm_train_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64]),
     "bgcn_lstm_train_grad": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "bgcn_bert_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int]),
+    "bgcn_bert_eval": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

@@ -1,0 +1,355 @@
+"""The TreeBERT baseline of the PHEME comparison (``model/Twitter/BERT_Twitter.py``), evaluation and
+explain.
+
+``TreeBERT`` holds the reference's parameters key for key (``BERT.embeddings...``, ``BERT.encoder.
+layer.{i}...``, ``BERT.pooler.dense.*``, ``fc.*``: ``BertModel``'s names and shapes), so a
+checkpoint's ``model_state_dict`` loads with ``strict=True``; ``transformers`` is not imported and
+nothing is downloaded.  The reference runs ``BertModel(is_decoder=True)`` on ``inputs_embeds`` once
+per tree inside a Python loop; here a whole batch of trees is one native call (``bgcn_bert_eval``).
+
+The class is a function of each tree's first row alone: ``is_decoder=True`` makes self-attention
+causal, the pooler reads position 0, position 0 attends to itself only and a softmax over one key
+is exactly 1.  :meth:`TreeBERT.evaluate`, :meth:`TreeBERT.validate`, :meth:`TreeBERT.forward` and
+a plain :meth:`TreeBERT.forward_batch` therefore run the *root-only* form: a chain of ``[B, hidden]``
+GEMMs with no q, k or score work.  The explain run needs every row (``last_hidden_state`` and the
+attention probabilities): :meth:`TreeBERT.explain_batch` and ``forward_batch(..., return_hidden /
+return_sums)`` run the *full* form, the causal encoder over all rows.
+
+Evaluation only: the per-tree ``forward`` raises in training mode (no autograd path, no dropout).
+"""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+
+import torch
+
+from . import _lib
+from ._lib import check, ptr, stream_handle
+
+_LAYER_FIELDS = (("q_w", "attention.self.query.weight"), ("q_b", "attention.self.query.bias"),
+                 ("k_w", "attention.self.key.weight"), ("k_b", "attention.self.key.bias"),
+                 ("v_w", "attention.self.value.weight"), ("v_b", "attention.self.value.bias"),
+                 ("ao_w", "attention.output.dense.weight"), ("ao_b", "attention.output.dense.bias"),
+                 ("ao_ln_w", "attention.output.LayerNorm.weight"), ("ao_ln_b", "attention.output.LayerNorm.bias"),
+                 ("i_w", "intermediate.dense.weight"), ("i_b", "intermediate.dense.bias"),
+                 ("o_w", "output.dense.weight"), ("o_b", "output.dense.bias"),
+                 ("o_ln_w", "output.LayerNorm.weight"), ("o_ln_b", "output.LayerNorm.bias"))
+_TOP_FIELDS = (("pos_emb", "BERT.embeddings.position_embeddings.weight"),
+               ("type_emb", "BERT.embeddings.token_type_embeddings.weight"),   # row 0 is the tensor's start
+               ("emb_ln_w", "BERT.embeddings.LayerNorm.weight"), ("emb_ln_b", "BERT.embeddings.LayerNorm.bias"),
+               ("pooler_w", "BERT.pooler.dense.weight"), ("pooler_b", "BERT.pooler.dense.bias"),
+               ("fc_w", "fc.weight"), ("fc_b", "fc.bias"))
+LN_EPS = 1e-12   # BertConfig.layer_norm_eps
+
+
+def _holder(**children):
+    m = torch.nn.Module()
+    for name, child in children.items():
+        m.add_module(name, child)
+    return m
+
+
+def _bert_holders(hidden, intermediate, num_layers, max_pos, vocab):
+    """``BertModel``'s parameter tree as plain torch.nn holders (their forwards are never called)."""
+    Lin, LN, Emb = torch.nn.Linear, torch.nn.LayerNorm, torch.nn.Embedding
+
+    def layer():
+        return _holder(
+            attention=_holder(self=_holder(query=Lin(hidden, hidden), key=Lin(hidden, hidden), value=Lin(hidden, hidden)),
+                              output=_holder(dense=Lin(hidden, hidden), LayerNorm=LN(hidden, eps=LN_EPS))),
+            intermediate=_holder(dense=Lin(hidden, intermediate)),
+            output=_holder(dense=Lin(intermediate, hidden), LayerNorm=LN(hidden, eps=LN_EPS)))
+
+    return _holder(
+        embeddings=_holder(word_embeddings=Emb(vocab, hidden), position_embeddings=Emb(max_pos, hidden),
+                           token_type_embeddings=Emb(2, hidden), LayerNorm=LN(hidden, eps=LN_EPS)),
+        encoder=_holder(layer=torch.nn.ModuleList([layer() for _ in range(num_layers)])),
+        pooler=_holder(dense=Lin(hidden, hidden)))
+
+
+@dataclass
+class BertExplanation:
+    """What :meth:`TreeBERT.explain_batch` returns: ``prediction`` [B] and ``log_probs`` [B, C];
+    ``hidden_sum`` / ``attn_sum`` [N] (per node: ``last_hidden_state`` summed over the features,
+    and the attention probabilities summed over layers, heads and queries per key); per tree their
+    rankings ``hidden_order`` / ``attn_order`` [N] int32 (local node indices, best first) with the
+    values in that order (``hidden_sorted`` / ``attn_sorted``); ``batch`` is the batch's."""
+    prediction: torch.Tensor
+    log_probs: torch.Tensor
+    hidden_sum: torch.Tensor
+    attn_sum: torch.Tensor
+    hidden_order: torch.Tensor
+    hidden_sorted: torch.Tensor
+    attn_order: torch.Tensor
+    attn_sorted: torch.Tensor
+    batch: torch.Tensor
+
+    def to_reference_dict(self, t: int) -> dict:
+        """Tree ``t``'s record as ``explain_PHEME.py:581-600`` builds it: ``bert_last_hidden_sum_top_k``
+        and ``bert_attentions_top_k`` are ``[indices, values]`` in plain lists, ``prediction`` an int."""
+        B = int(self.log_probs.size(0))
+        if not 0 <= t < B:
+            raise IndexError("tree index out of range")
+        sel = (self.batch == t).nonzero().flatten()
+        a, b = (int(sel[0]), int(sel[-1]) + 1) if sel.numel() else (0, 0)
+        return {"bert_last_hidden_sum_top_k": [self.hidden_order[a:b].tolist(), self.hidden_sorted[a:b].tolist()],
+                "bert_attentions_top_k": [self.attn_order[a:b].tolist(), self.attn_sorted[a:b].tolist()],
+                "prediction": int(self.prediction[t])}
+
+
+class TreeBERT(torch.nn.Module):
+    """Drop-in for the reference's ``TreeBERT`` (``BERT_Twitter.py:20-42``) in eval mode.
+
+    The positional signature is the reference's, which ignores ``in_feats``, ``hid_feats`` and
+    ``out_feats`` (they are stored): its encoder is BERT-base and its head ``Linear(768, 4)``.  The
+    keywords give the encoder's sizes (defaults: BERT-base) and ``num_classes`` the head's width, so
+    the default module has exactly the reference's ``state_dict``.  Initialisation is BERT's: normal
+    with std 0.02, LayerNorm weights 1 and biases 0, every other bias 0.
+
+    ``forward(data)`` is the reference's per-tree call; :meth:`forward_batch`, :meth:`evaluate`,
+    :meth:`validate` and :meth:`explain_batch` run a whole batch of trees per native call."""
+
+    def __init__(self, in_feats=256 * 768, hid_feats=64, out_feats=64, device=None, pooling='max', version=0, *,
+                 hidden=768, heads=12, intermediate=3072, num_layers=12, max_pos=512, vocab=30522, num_classes=4):
+        super().__init__()
+        self.in_feats, self.hid_feats, self.out_feats = in_feats, hid_feats, out_feats
+        self.hidden, self.heads, self.intermediate, self.num_layers = hidden, heads, intermediate, num_layers
+        self.max_pos = max_pos
+        self.BERT = _bert_holders(hidden, intermediate, num_layers, max_pos, vocab)
+        self.fc = torch.nn.Linear(hidden, num_classes)
+        with torch.no_grad():
+            for m in self.BERT.modules():
+                if isinstance(m, (torch.nn.Linear, torch.nn.Embedding)):
+                    m.weight.normal_(mean=0.0, std=0.02)
+                    if getattr(m, "bias", None) is not None:
+                        m.bias.zero_()
+        self.device = device
+        self.pooling = pooling
+        self.version = version
+        # a checkpoint written by an older transformers also holds this buffer: dropped on load
+        self._register_load_state_dict_pre_hook(
+            lambda sd, prefix, *_: sd.pop(prefix + "BERT.embeddings.position_ids", None))
+        if device is not None:
+            self.to(device)
+
+    @property
+    def num_classes(self) -> int:
+        return self.fc.out_features
+
+    # ---- parameters
+    def names(self):
+        """The ``state_dict`` names the native call reads, in the order of its argument struct."""
+        return [n for _, n in _TOP_FIELDS] + [f"BERT.encoder.layer.{i}.{n}" for i in range(self.num_layers)
+                                              for _, n in _LAYER_FIELDS]
+
+    def _bind(self, dev):
+        """The argument struct, refilled only when a parameter was rebound, moved or (a tensor the
+        kernels cannot read in place: not fp32 / contiguous / 16-byte aligned / on ``dev``) changed."""
+        by_name = dict(self.named_parameters())
+        src = [by_name[n] for n in self.names()]
+        direct = [t.dtype == torch.float32 and t.is_contiguous() and t.device == dev and t.data_ptr() % 16 == 0
+                  for t in src]
+        key = (dev,) + tuple((t.data_ptr(), t.dtype, None if ok else t._version) for t, ok in zip(src, direct))
+        st = self.__dict__.get("_state")
+        if st is not None and st["key"] == key:
+            return st
+        held = [t.detach() if ok else t.detach().to(device=dev, dtype=torch.float32).contiguous().clone()
+                for t, ok in zip(src, direct)]
+        a = _lib.BertArgs()
+        it = iter(held)
+        for field, _ in _TOP_FIELDS:
+            setattr(a, field, next(it).data_ptr())
+        for i in range(self.num_layers):
+            for field, _ in _LAYER_FIELDS:
+                setattr(a.layer[i], field, next(it).data_ptr())
+        a.hidden, a.heads, a.intermediate, a.num_layers = self.hidden, self.heads, self.intermediate, self.num_layers
+        a.max_pos, a.out_feats, a.ln_eps = self.max_pos, self.num_classes, LN_EPS
+        if st is None or st["status"].device != dev:
+            st = {"status": torch.zeros(1, dtype=torch.int32, device=dev),
+                  "seen": torch.zeros(1, dtype=torch.int32, device=dev), "sizes": {}, "ws": {}}
+            self.__dict__["_state"] = st
+        a.status = st["status"].data_ptr()
+        st.update(key=key, args=a, held=held)
+        return st
+
+    def _pool(self, x):
+        """[n, T, hidden] -> [n, hidden] over T (``BERT_Twitter.py:34-37``), one torch reduction."""
+        if self.pooling == 'max':
+            return x.amax(dim=1)
+        if self.pooling == 'mean':
+            return x.mean(dim=1)
+        raise ValueError(f"pooling must be 'max' or 'mean', not {self.pooling!r}")
+
+    # ---- the native call
+    def _workspace(self, st, N, B, full, dev):
+        """The form's workspace, asked for again only when ``(N, B)`` changes; never shrinks."""
+        if st["sizes"].get(full) != (N, B):
+            need = _lib.lib().bgcn_bert_workspace_size(N, B, self.hidden, self.intermediate, self.num_layers, int(full))
+            if need == 0:
+                raise _lib.BGCNError("bgcn_bert_eval: unsupported shape (hidden = 64 heads in [64, 1024], intermediate "
+                                     "% 64 in [64, 4096], num_layers in [1, 24])")
+            if st["ws"].get(full) is None or st["ws"][full].numel() < need or st["ws"][full].device != dev:
+                st["ws"][full] = _lib.workspace(need, dev)
+            st["sizes"][full] = (N, B)
+        return st["ws"][full]
+
+    def _run(self, x, rootindex, y=None, logp=None, want_pred=False, want_hidden=False, want_sums=False, hidden=None):
+        if not x.is_cuda:
+            raise _lib.BGCNError("bigcn_amd ops take device tensors (no CPU path)")
+        if x.dim() != 2 or x.size(1) != self.hidden:
+            raise ValueError(f"the sequences' rows must be [N, {self.hidden}], got {tuple(x.shape)}")
+        dev = x.device
+        st = self._bind(dev)
+        if not (x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+                and x.stride(0) >= x.size(1)):
+            x = x.float().contiguous()
+        rootindex = rootindex.to(device=dev, dtype=torch.int64).contiguous()
+        N, B, C = int(x.size(0)), int(rootindex.numel()), self.num_classes
+        if N < 1 or B < 1:
+            raise ValueError("the batch needs at least one row and one tree")
+        if y is not None:
+            y = y.to(device=dev, dtype=torch.int64).contiguous()
+            if y.numel() != B:
+                raise ValueError("y must have one label per tree")
+        if logp is None:
+            logp = torch.empty(B, C, dtype=torch.float32, device=dev)
+        elif logp.dtype != torch.float32 or not logp.is_contiguous() or logp.numel() != B * C or logp.device != dev:
+            raise ValueError("logp must be a contiguous fp32 [B, num_classes] tensor")
+        if hidden is None and want_hidden:
+            hidden = torch.empty(N, self.hidden, dtype=torch.float32, device=dev)
+        elif hidden is not None and (hidden.dtype != torch.float32 or not hidden.is_contiguous()
+                                     or hidden.numel() != N * self.hidden or hidden.device != dev):
+            raise ValueError("hidden must be a contiguous fp32 [N, hidden] tensor")
+        full = hidden is not None or want_sums
+        ws = self._workspace(st, N, B, full, dev)
+        r = {"logp": logp, "hidden": hidden,
+             "loss": torch.empty(1, dtype=torch.float32, device=dev) if y is not None else None,
+             "correct": torch.empty(1, dtype=torch.int32, device=dev) if y is not None else None,
+             "pred": torch.empty(B, dtype=torch.int64, device=dev) if want_pred else None,
+             # [2, N] with a row stride of whole 16-byte units: hidden_sum, attn_sum
+             "sums": torch.empty(2, (N + 3) // 4 * 4, dtype=torch.float32, device=dev)[:, :N] if want_sums else None}
+        a = st["args"]
+        a.x, a.ldx, a.num_nodes = x.data_ptr(), x.stride(0), N
+        a.seq_start, a.num_seqs = rootindex.data_ptr(), B
+        a.y, a.logp, a.loss, a.correct, a.pred = ptr(y), logp.data_ptr(), ptr(r["loss"]), ptr(r["correct"]), ptr(r["pred"])
+        a.hidden_out = ptr(hidden)
+        a.hidden_sum = r["sums"][0].data_ptr() if want_sums else 0
+        a.attn_sum = r["sums"][1].data_ptr() if want_sums else 0
+        check(_lib.lib().bgcn_bert_eval(ctypes.addressof(a), ptr(ws), ws.numel(), stream_handle()))
+        st["seen"].bitwise_or_(st["status"])   # the call zeroes its status word; check_status reads this one
+        return r
+
+    def forward(self, data):
+        """The reference's per-tree call, on the root-only form (no host sync).  ``version != 2``:
+        ``data [n, T, hidden]`` is pooled over ``T`` and run as one sequence of ``n`` rows, giving
+        ``[1, num_classes]`` log probabilities.  ``version == 2``: ``data [n, T, hidden]`` is ``n``
+        sequences of ``T`` tokens, giving ``[n, num_classes]``."""
+        if self.training:
+            raise NotImplementedError("bigcn_amd.TreeBERT.forward is the per-tree evaluation call and has no autograd "
+                                      "path: training TreeBERT is not implemented here, call model.eval()")
+        if data.dim() != 3:
+            raise ValueError(f"data must be [n, T, {self.hidden}], got {tuple(data.shape)}")
+        if self.version == 2:
+            n, T = int(data.size(0)), int(data.size(1))
+            root = torch.arange(n, dtype=torch.int64, device=data.device) * T
+            return self._run(data.reshape(n * T, -1), root)["logp"]
+        root = torch.zeros(1, dtype=torch.int64, device=data.device)
+        return self._run(self._pool(data), root)["logp"]
+
+    def forward_batch(self, x, rootindex, return_hidden=False, return_sums=False):
+        """``logp [B, num_classes]`` of a batch of trees: tree ``b`` is the rows ``[rootindex[b],
+        rootindex[b + 1])`` of ``x [N, hidden]`` (the last one runs to ``N``), as the reference slices.
+        No host sync; a tree longer than ``max_pos`` is flagged (:meth:`check_status`), never truncated.
+
+        Alone this is the root-only form and reads the trees' first rows only.  ``return_hidden=True``
+        also returns ``last_hidden_state [N, hidden]``, ``return_sums=True`` also ``(hidden_sum [N],
+        attn_sum [N])``; either runs the full causal encoder, and ``logp`` then comes from its own
+        root rows."""
+        r = self._run(x, rootindex, want_hidden=return_hidden, want_sums=return_sums)
+        out = (r["logp"],)
+        if return_hidden:
+            out += (r["hidden"],)
+        if return_sums:
+            out += ((r["sums"][0], r["sums"][1]),)
+        return out if len(out) > 1 else out[0]
+
+    def _root_rows(self, data):
+        """``[N, hidden]`` holding the pooled row of every tree's root; the other rows are left
+        unwritten, as the root-only form never reads them.  Only ``B`` of the ``N`` rows of ``data.x``
+        are pooled (the indices are clamped for this gather; the native call flags a bad one)."""
+        x = data.x
+        N = int(x.size(0))
+        roots = data.rootindex.to(device=x.device, dtype=torch.int64).clamp(0, max(N - 1, 0))
+        pooled = self._pool(x.index_select(0, roots).reshape(roots.numel(), -1, self.hidden).float())
+        rows = torch.empty(N, self.hidden, dtype=torch.float32, device=x.device)
+        rows[roots] = pooled
+        return rows
+
+    def evaluate(self, data, logp=None, pred=False):
+        """One batch of the reference's test loop (``BERT_Twitter.py:127-150``) as one native call on the
+        root-only form, in eval mode whatever ``model.training`` says: ``data.x`` is reshaped to ``[N,
+        -1, hidden]`` and pooled over the middle axis - only the ``B`` root rows are pooled, the class
+        does not depend on any other; labels ``data.y``.
+
+        Returns ``(loss, correct)`` (0-dim fp32 / int32 device tensors), plus ``pred`` ([B] int64) when
+        ``pred=True``.  No host sync.  Validity of the batch: :meth:`check_status`."""
+        if self.version == 2:
+            raise NotImplementedError("TreeBERT.evaluate with version == 2: the reference's loop body assigns the "
+                                      "[n, 4] result of an n-node tree into one row of out_labels "
+                                      "(BERT_Twitter.py:103-105), which fails for any tree of more than one node")
+        r = self._run(self._root_rows(data), data.rootindex, y=data.y, logp=logp, want_pred=pred)
+        out = (r["loss"].view(()), r["correct"].view(()))
+        return out + (r["pred"],) if pred else out
+
+    def validate(self, batches, metrics=None):
+        """The reference's test loop without a host sync: every batch goes through ``evaluate(batch,
+        pred=True)`` and its loss, correct count, predictions and labels into ``metrics.add(...)``
+        (:class:`bigcn_amd.metrics.EpochMetrics`; by default a new one sized for ``batches``)."""
+        from .metrics import EpochMetrics
+        batches = list(batches)
+        if metrics is None:
+            if not batches:
+                raise ValueError("validate needs at least one batch")
+            metrics = EpochMetrics(int(self.num_classes), len(batches), batches[0].y.device)
+        elif len(metrics) + len(batches) > metrics.max_batches:
+            raise IndexError(f"metrics has room for {metrics.max_batches - len(metrics)} more batches, "
+                             f"{len(batches)} given")
+        for batch in batches:
+            loss, correct, pred = self.evaluate(batch, pred=True)
+            metrics.add(pred, batch.y, loss, correct)
+        return metrics
+
+    def explain_batch(self, data) -> BertExplanation:
+        """The BERT branch of the explain run (``explain_PHEME.py:581-600``) for a whole batch: one
+        full-form call on all rows of ``data.x`` (reshaped to ``[N, -1, hidden]`` and pooled), then
+        ``bgcn_segment_rank`` on ``hidden_sum`` and ``attn_sum`` - per-tree ``topk`` with ``k = n``,
+        ties by ascending node index.  ``data.batch`` is the PyG batch vector.  One host sync at the
+        end (the status words)."""
+        from .ops import _segment_rank
+        if self.training:
+            raise ValueError("explain needs the model in eval mode (call model.eval())")
+        with torch.no_grad():
+            x = data.x
+            rows = self._pool(x.reshape(x.size(0), -1, self.hidden).float())
+            r = self._run(rows, data.rootindex, want_pred=True, want_sums=True)
+            status = torch.zeros(1, dtype=torch.int32, device=x.device)
+            order, srt = _segment_rank(r["sums"], data.batch, int(data.rootindex.numel()), status)
+            self.check_status()
+            if int(status.item()) & 1:
+                raise IndexError("the batch vector decreases or holds an id outside [0, B)")
+        return BertExplanation(r["pred"], r["logp"], r["sums"][0], r["sums"][1], order[0], srt[0], order[1], srt[1],
+                               data.batch)
+
+    def check_status(self) -> None:
+        """One host sync: raise ``IndexError`` when any batch evaluated since the last check held a
+        ``rootindex`` that does not increase strictly or lies outside ``[0, N)``, a tree longer than
+        ``max_pos``, or a label outside ``[0, num_classes)``."""
+        st = self.__dict__.get("_state")
+        if st is None:
+            return
+        s = int(st["seen"].item())
+        st["seen"].zero_()
+        if s & _lib.BGCN_STATUS_SEQUENCE:
+            raise IndexError("the batch holds a rootindex that does not increase strictly or is out of range, "
+                             "a tree longer than max_pos, or a label outside [0, num_classes)")

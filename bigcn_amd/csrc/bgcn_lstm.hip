@@ -197,34 +197,7 @@ __global__ __launch_bounds__(256) void k_lstm_head(LstmHeadArgs a) {
   }
   __syncthreads();
   if (w != 0) return;
-  const bool in = l < a.C;
-  const float zc = in ? z[l] : -INFINITY;
-  float mx = zc;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-  const float lse = mx + logf(wave_sum(in ? expf(zc - mx) : 0.f));
-  const float lp = zc - lse;
-  if (in && a.logp) a.logp[b * a.C + l] = lp;
-  float bv = lp;
-  int bi = l;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {   // the first maximal class, as torch's max
-    const float ov = __shfl_xor(bv, o);
-    const int oi = __shfl_xor(bi, o);
-    if (ov > bv || (ov == bv && oi < bi)) {
-      bv = ov;
-      bi = oi;
-    }
-  }
-  const int64_t yb = a.y ? a.y[b] : 0;
-  const bool yok = a.y && yb >= 0 && yb < a.C;
-  const float ly = __shfl(lp, yok ? int(yb) : 0);
-  if (l == 0) {
-    a.loss_row[b] = yok ? -ly : 0.f;
-    a.predw[b] = bi;
-    if (a.pred) a.pred[b] = bi;
-    if (a.y && !yok) atomicOr(a.status, BGCN_STATUS_SEQUENCE);
-  }
+  seq_head_tail(z, a.C, b, l, a.y, a.logp, a.loss_row, a.predw, a.pred, a.status);
 }
 
 // the mean NLL and the correct count over the sequences: strided thread sums, then a halving tree
@@ -262,6 +235,14 @@ __global__ __launch_bounds__(256) void k_lstm_finish(const float* __restrict__ l
 bool lstm_shape_ok(int64_t N, int64_t B, int64_t F, int64_t H, int64_t L) {
   return N > 0 && B > 0 && N < (int64_t(1) << 31) - 1 && B < (int64_t(1) << 31) - 1 && F > 0 && F % 4 == 0 &&
          F < (int64_t(1) << 31) && H % 64 == 0 && H >= 64 && H <= 1024 && L >= 1 && L <= kMaxLayers;
+}
+
+int seq_finish(const float* loss_row, const int32_t* predw, const int64_t* y, int64_t B, float* loss,
+               int32_t* correct, hipStream_t s) {
+  if (!loss && !correct) return BGCN_OK;
+  hipLaunchKernelGGL(k_lstm_finish, dim3(1), dim3(256), 0, s, loss_row, predw, y, B, loss, correct);
+  BGCN_CHECK_LAUNCH();
+  return BGCN_OK;
 }
 
 int lstm_check_args(const bgcn_lstm_args* a, const void* ws) {
@@ -320,11 +301,7 @@ int lstm_forward(const bgcn_lstm_args* a, const LstmFwdWs& w, bool save, float* 
                   a->y, a->logp, h_n, w.loss_row, w.predw, a->pred, a->status};
   hipLaunchKernelGGL(k_lstm_head, dim3(unsigned(B)), dim3(256), 0, s, hd);
   BGCN_CHECK_LAUNCH();
-  if (a->loss || a->correct) {
-    hipLaunchKernelGGL(k_lstm_finish, dim3(1), dim3(256), 0, s, w.loss_row, w.predw, a->y, B, a->loss, a->correct);
-    BGCN_CHECK_LAUNCH();
-  }
-  return BGCN_OK;
+  return seq_finish(w.loss_row, w.predw, a->y, B, a->loss, a->correct, s);
 }
 
 int lstm_eval_impl(const bgcn_lstm_args* a, void* ws, size_t ws_bytes, hipStream_t s) {

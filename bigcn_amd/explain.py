@@ -180,12 +180,16 @@ class Explanation:
 def explain(model, data, batch_of_one: bool = False) -> Explanation:
     """The body of ``explain_PHEME.py``'s per-sample loop (``:530-607``) for a whole batch:
     ``model`` is a ``BiGCN``, ``Net`` or ``EBGCN`` of this package in eval mode (``ValueError``
-    otherwise), ``data`` a normal multi-tree batch.  Runs under ``torch.no_grad()`` with one host
+    otherwise), ``data`` a normal multi-tree batch.  A ``TreeBERT`` takes the BERT branch (``:581-600``)
+    and returns its :class:`bigcn_amd.bert.BertExplanation` (:meth:`TreeBERT.explain_batch`).  Runs under ``torch.no_grad()`` with one host
     sync at the end; an index out of range, or a ``batch`` vector that decreases, raises
     ``IndexError``.  ``batch_of_one``: see :func:`explain_direction`; it changes the stage sums
     only, ``log_probs`` are always the model's normal forward on ``data``."""
     if model.training:
         raise ValueError("explain needs the model in eval mode (call model.eval())")
+    from .bert import TreeBERT
+    if isinstance(model, TreeBERT):
+        return model.explain_batch(data)
     with torch.no_grad():
         status = torch.zeros(1, dtype=torch.int32, device=data.x.device)
         B = _num_graphs(data)

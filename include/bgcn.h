@@ -1253,6 +1253,101 @@ size_t bgcn_lstm_train_workspace_size(int64_t num_nodes, int64_t num_seqs, int64
 int bgcn_lstm_train_grad(const bgcn_lstm_train_args* args, void* workspace, size_t workspace_bytes,
                          bgcn_stream_t stream);
 
+/* --------------------------------------------------------------------------
+ * TreeBERT baseline, evaluation and explain: the test loop body of model/Twitter/BERT_Twitter.py
+ * (:20-42, :86-110) and the BERT branch of explain_PHEME.py (:581-600) for a whole batch of trees
+ * as one call: one launch sequence, no host round trip, no allocation (everything lives in the
+ * caller's workspace).  Additive entry points: BGCN_ABI_VERSION is unchanged.
+ *
+ * The model is BertModel(is_decoder = True) fed inputs_embeds in eval mode with no attention mask,
+ * then fc(pooler_output) and log_softmax.  Sequence b is the rows [seq_start[b], seq_start[b + 1])
+ * of x (the last one runs to num_nodes), n of them, x[t] its row t:
+ *   embeddings  h = LN(x[t] + position_embeddings[t] + token_type_embeddings[0])
+ *               (LN: biased variance, eps = ln_eps; word_embeddings is never read)
+ *   per layer   q, k, v = Linear(h); per head (width 64): P = softmax(q k^T / 8) over the keys
+ *               j <= t, ctx = P v;  a = LN(dense(ctx) + h);  o = LN(dense2(gelu(dense1(a))) + a),
+ *               gelu(x) = x 0.5 (1 + erf(x / sqrt 2))
+ *   head        pooled = tanh(pooler.dense(o_last[0])); logp = log_softmax(fc(pooled))
+ * With y, loss = the mean NLL, pred = the first maximal class (torch's max), correct = the number
+ * of sequences with pred == y; without y, loss and correct are 0.
+ *
+ * Root-only form (hidden, hidden_sum and attn_sum all NULL).  Row 0 attends to itself only and a
+ * softmax over one key is exactly 1, so pooled is a function of the sequence's first row alone:
+ * the call gathers the B root rows and runs embeddings + LN at position 0, then per layer the
+ * value projection, the attention-output dense, the intermediate and output GEMMs with their row
+ * kernels on [B, hidden].  No q, k or score is computed and no other row of x is read.
+ *
+ * Full form (any of the three given).  Every row goes through every layer; attention is a causal
+ * two-pass kernel on the fp32 MFMA, one wave per (sequence, head, tile of 32 queries): pass 1 the
+ * row maxima and normalisers over the key tiles, pass 2 the normalised P, ctx = P v and P's column
+ * sums.  hidden [N, hidden] is last_hidden_state, hidden_sum [N] its row sums, attn_sum [N] per
+ * key the sum of P over layers, heads and queries (attention_head.sum(-2).sum(1) summed over the
+ * layers), reduced through workspace partials in a fixed order.  Rows before seq_start[0] belong to
+ * no sequence: their hidden, hidden_sum and attn_sum are zeros.  logp comes from the full pass's own
+ * row 0 of each sequence (the root-only chain is not run beside it).  Deterministic: no float
+ * atomics, fixed summation orders.
+ *
+ * The launch grid covers max_pos queries per sequence with early exit: there is no max_len
+ * argument and no host sync.
+ *
+ * Validity is decided on the device.  *status is zeroed by the call; BGCN_STATUS_SEQUENCE is set by
+ * a seq_start that does not increase strictly, a start outside [0, num_nodes), a sequence longer
+ * than max_pos (an index error in the reference; never truncated here), or a label outside
+ * [0, out_feats).  A fault in seq_start or a length empties every sequence: nothing out of bounds
+ * is read or written, every row counts as outside any sequence, and the results are not to be
+ * used; a bad label contributes no loss.
+ *
+ * BGCN_EINVAL before any HIP call: hidden not 64 heads or outside [64, 1024], intermediate not a
+ * multiple of 64 in [64, 4096], num_layers outside [1, 24], max_pos outside [1, 512], out_feats
+ * outside [1, 64] ("unsupported shape"; bgcn_bert_workspace_size returns 0 for these), a null or
+ * not 16-byte aligned pointer (x, ldx, every weight, logp, the optional outputs, the workspace),
+ * "workspace too small".
+ * -------------------------------------------------------------------------- */
+#define BGCN_BERT_MAX_LAYERS 24
+#define BGCN_BERT_QUERY_TILE 32   /* queries per workgroup of the attention kernel */
+typedef struct bgcn_bert_layer {
+  const float *q_w, *q_b, *k_w, *k_b, *v_w, *v_b;   /* attention.self: [hidden, hidden], [hidden] */
+  const float *ao_w, *ao_b, *ao_ln_w, *ao_ln_b;     /* attention.output.dense / LayerNorm         */
+  const float *i_w, *i_b;                           /* intermediate.dense: [intermediate, hidden] */
+  const float *o_w, *o_b, *o_ln_w, *o_ln_b;         /* output.dense [hidden, intermediate] / LN   */
+} bgcn_bert_layer;
+typedef struct bgcn_bert_args {
+  const float* x;                /* [N, ldx] fp32, hidden columns used        */
+  int64_t ldx;
+  int64_t num_nodes;             /* N                                         */
+  const int64_t* seq_start;      /* [B] first row of each sequence            */
+  int64_t num_seqs;              /* B                                         */
+  int64_t hidden;                /* 64 heads                                  */
+  int64_t heads;
+  int64_t intermediate;
+  int64_t num_layers;
+  int64_t max_pos;               /* rows of pos_emb: the longest sequence     */
+  int64_t out_feats;             /* C                                         */
+  float ln_eps;
+  int32_t reserved;
+  const float* pos_emb;          /* [max_pos, hidden]                         */
+  const float* type_emb;         /* [hidden]: token_type_embeddings row 0     */
+  const float* emb_ln_w;         /* [hidden]                                  */
+  const float* emb_ln_b;
+  bgcn_bert_layer layer[BGCN_BERT_MAX_LAYERS];
+  const float* pooler_w;         /* [hidden, hidden]                          */
+  const float* pooler_b;
+  const float* fc_w;             /* [C, hidden]                               */
+  const float* fc_b;
+  const int64_t* y;              /* [B] labels, or NULL                       */
+  float* logp;                   /* [B, C]                                    */
+  float* loss;                   /* [1] mean NLL, or NULL                     */
+  int32_t* correct;              /* [1] or NULL                               */
+  int64_t* pred;                 /* [B] or NULL                               */
+  float* hidden_out;             /* [N, hidden] last_hidden_state, or NULL    */
+  float* hidden_sum;             /* [N] or NULL                               */
+  float* attn_sum;               /* [N] or NULL                               */
+  int32_t* status;               /* [1]                                       */
+} bgcn_bert_args;
+size_t bgcn_bert_workspace_size(int64_t num_nodes, int64_t num_seqs, int64_t hidden, int64_t intermediate,
+                                int64_t num_layers, int want_full);
+int bgcn_bert_eval(const bgcn_bert_args* args, void* workspace, size_t workspace_bytes, bgcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

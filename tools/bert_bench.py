@@ -1,0 +1,128 @@
+"""Time the batched TreeBERT calls (bigcn_amd.TreeBERT, one native call per batch) against the
+reference's form on the same GPU, weights and batch: the per-tree Python loop of the full 12-layer
+encoder (model/Twitter/BERT_Twitter.py:127-150, with its rootindex.tolist() sync).
+
+    python tools/bert_bench.py --out profiles/bert_eval.json
+
+One batch at the PHEME shape: B = 24 trees (sizes from synth_tree_sizes at mean 64, capped at 512),
+rows of T x 768 values pooled to 768, BERT-base sizes (12 layers, 768 wide, 12 heads, 3072
+intermediate), random weights.  Timed: ``evaluate`` (the root-only form), the full-form call
+(``forward_batch(..., return_hidden=True, return_sums=True)`` on the pooled rows) and the reference
+loop - ``transformers``' BertModel where importable, else the fp32 torch restatement of
+tests/bert_ref.py.  The root-only call is bound by the weight bytes it reads once per call; its
+achieved fraction of the HBM peak is reported against them.  Times are host clocks around work that
+ends in a device synchronise, after a warm-up.  There is no fallback: without a GPU the script fails."""
+import argparse
+import json
+import os
+import sys
+import time
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from bigcn_amd import TreeBERT                               # noqa: E402
+from bigcn_amd.data import synth_tree_sizes                  # noqa: E402
+
+HBM_PEAK_GBS = 8000.0   # MI355X: 8 TB/s
+
+
+def timed(fn, warmup, iters):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(iters):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return {"median_ms": float(np.median(ts)), "min_ms": float(np.min(ts)), "max_ms": float(np.max(ts))}
+
+
+def reference(model):
+    """``(which, encode)``: encode(rows [n, 768]) -> pooler_output [768] of one tree."""
+    sd = {k: v for k, v in model.state_dict().items()}
+    try:
+        import transformers as tr
+    except ImportError:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import bert_ref
+        return "torch restatement (tests/bert_ref.py), fp32", lambda rows: torch.tanh(F.linear(
+            bert_ref.encode(sd, rows, model.num_layers, model.heads)[0][0], sd["BERT.pooler.dense.weight"],
+            sd["BERT.pooler.dense.bias"]))
+    cfg = tr.BertConfig(vocab_size=sd["BERT.embeddings.word_embeddings.weight"].size(0), hidden_size=model.hidden,
+                        num_hidden_layers=model.num_layers, num_attention_heads=model.heads,
+                        intermediate_size=model.intermediate, max_position_embeddings=model.max_pos, is_decoder=True)
+    bert = tr.BertModel(cfg).to(model.fc.weight.device).eval()
+    bert.load_state_dict({k[5:]: v for k, v in sd.items() if k.startswith("BERT.")}, strict=False)
+    return f"transformers {tr.__version__} BertModel(is_decoder=True), fp32", \
+        lambda rows: bert(inputs_embeds=rows.unsqueeze(0)).pooler_output[0]
+
+
+@torch.no_grad()
+def reference_loop(model, encode, data, rows):
+    """One batch of the reference's test loop, as written there (pooled rows given)."""
+    rootindices = data.rootindex.tolist()
+    out = torch.zeros(data.y.shape[0], model.num_classes, device=rows.device)
+    for k, r in enumerate(rootindices):
+        sl = rows[r:] if k == len(rootindices) - 1 else rows[r:rootindices[k + 1]]
+        out[k] = F.log_softmax(model.fc(encode(sl)), dim=-1)
+    loss = F.nll_loss(out, data.y)
+    return out, loss.item(), out.max(dim=1)[1].eq(data.y).sum().item()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join("profiles", "bert_eval.json"))
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--ref-iters", type=int, default=3)
+    ap.add_argument("--tokens", type=int, default=4, help="T: values pooled per row are T x 768")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bert_bench needs a ROCm GPU (no fallback)")
+    dev = torch.device("cuda:0")
+    B, seed = 24, 1
+    sizes = np.minimum(synth_tree_sizes(np.random.default_rng(seed), B, 64), 512)
+    N = int(sizes.sum())
+    g = torch.Generator().manual_seed(seed)
+    data = SimpleNamespace(x=torch.randn(N, a.tokens * 768, generator=g).to(dev),
+                           rootindex=torch.tensor(np.concatenate(([0], np.cumsum(sizes)[:-1])), dtype=torch.int64).to(dev),
+                           y=torch.randint(0, 4, (B,), generator=g).to(dev))
+    torch.manual_seed(seed)
+    model = TreeBERT(256 * 768, 64, 64, dev, vocab=8).eval()
+    rows = model._pool(data.x.reshape(N, -1, 768))
+    logp = torch.empty(B, 4, device=dev)
+
+    ev = timed(lambda: model.evaluate(data, logp=logp), a.warmup, a.iters)
+    full = timed(lambda: model.forward_batch(rows, data.rootindex, return_hidden=True, return_sums=True), a.warmup, a.iters)
+    model.check_status()
+    which, encode = reference(model)
+    ref = timed(lambda: reference_loop(model, encode, data, rows), 1, a.ref_iters)
+    want, _, _ = reference_loop(model, encode, data, rows)
+    read = [n for n in model.names() if ".query." not in n and ".key." not in n
+            and "position_embeddings" not in n and "token_type" not in n]
+    by_name = dict(model.named_parameters())
+    weight_bytes = 4 * sum(by_name[n].numel() for n in read)
+    gbs = weight_bytes / (ev["median_ms"] * 1e-3) / 1e9
+    res = {"device": torch.cuda.get_device_name(0), "B": B, "N": N, "tokens_per_row": a.tokens,
+           "longest_tree": int(sizes.max()), "evaluate_root_only": ev, "full_form": full, "reference_loop": ref,
+           "reference": which,
+           "ratio_reference_over_evaluate": ref["median_ms"] / ev["median_ms"],
+           "ratio_reference_over_full_form": ref["median_ms"] / full["median_ms"],
+           "root_only_weight_bytes": weight_bytes, "root_only_GBps": gbs,
+           "root_only_fraction_of_hbm_peak": gbs / HBM_PEAK_GBS, "hbm_peak_GBps": HBM_PEAK_GBS,
+           "max_abs_logp_diff_vs_reference": float((logp - want).abs().max())}
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
