@@ -2,7 +2,7 @@
 ``BertModel(is_decoder=True)`` on ``inputs_embeds``, eval mode, no attention mask, then ``fc`` and
 ``log_softmax``), looped over the trees one sequence at a time as the reference does, in fp64 (the
 oracle) or fp32 (torch's own arithmetic).  No ``transformers`` import.  Also the seeded cases shared
-by tests/test_bert.py and tests/test_gpu_bert.py."""
+by tests/test_bert.py, tests/test_gpu_bert.py (CASES) and tests/test_gpu_bert_edges.py (EDGE_CASES)."""
 import functools
 import math
 from types import SimpleNamespace
@@ -67,13 +67,14 @@ def gelu(v):
 
 def encode(sd, seq, layers, heads):
     """One sequence ``seq [n, hidden]`` -> (last_hidden_state [n, hidden], per layer the attention
-    probabilities [heads, n, n], the largest |score| that entered a softmax)."""
+    probabilities [heads, n, n], the largest |score| that entered a softmax, per layer head 0's
+    :func:`tile_gap` [n])."""
     n, hidden = seq.shape
     e = "BERT.embeddings."
     h = _ln(seq + sd[e + "position_embeddings.weight"][:n] + sd[e + "token_type_embeddings.weight"][0], sd,
             e + "LayerNorm")
     causal = torch.ones(n, n, dtype=torch.bool).tril()
-    probs, top = [], 0.0
+    probs, top, gaps = [], 0.0, []
     for i in range(layers):
         p = f"BERT.encoder.layer.{i}."
         q, k, v = (_lin(h, sd, p + "attention.self." + w).view(n, heads, 64).transpose(0, 1)
@@ -82,11 +83,26 @@ def encode(sd, seq, layers, heads):
         top = max(top, float(s[:, causal].abs().max()))
         P = torch.softmax(s.masked_fill(~causal, float("-inf")), dim=-1)
         probs.append(P)
+        gaps.append(tile_gap(s[0]))
         ctx = (P @ v).transpose(0, 1).reshape(n, hidden)
         a = _ln(_lin(ctx, sd, p + "attention.output.dense") + h, sd, p + "attention.output.LayerNorm")
         h = _ln(_lin(gelu(_lin(a, sd, p + "intermediate.dense")), sd, p + "output.dense") + a, sd,
                 p + "output.LayerNorm")
-    return h, probs, top
+    return h, probs, top, gaps
+
+
+def tile_gap(s):
+    """Per query row of one head's scores ``s [n, n]``: the largest causal score among the keys of the
+    later key tiles (key >= QUERY_TILE) minus the largest of the first tile's; nan for the rows that
+    reach no later tile.  Positive: the running maximum moves after tile 0 and the sum so far is
+    rescaled by exp(-gap); negative: the later tiles' terms are exp(gap) of the first's."""
+    n = s.size(0)
+    causal = torch.ones(n, n, dtype=torch.bool).tril()
+    first = s[:, :QUERY_TILE].masked_fill(~causal[:, :QUERY_TILE], float("-inf")).amax(-1)
+    if n <= QUERY_TILE:
+        return torch.full((n,), float("nan"), dtype=s.dtype)
+    later = s[:, QUERY_TILE:].masked_fill(~causal[:, QUERY_TILE:], float("-inf")).amax(-1)
+    return torch.where(torch.isinf(later), torch.full_like(later, float("nan")), later - first)
 
 
 def rank(values):
@@ -105,10 +121,11 @@ def run(sd, x, rootindex, layers, heads, y=None, dtype=torch.float64):
     N, B, hidden = x.size(0), len(roots), x.size(1)
     res = SimpleNamespace(hidden=torch.zeros(N, hidden, dtype=dtype), attn_sum=torch.zeros(N, dtype=dtype),
                           logp=torch.zeros(B, sd["fc.weight"].size(0), dtype=dtype), pooled=torch.zeros(B, hidden, dtype=dtype),
-                          row_max=[], top_score=0.0, rank_hidden=[], rank_attn=[], loss=None)
+                          row_max=[], top_score=0.0, rank_hidden=[], rank_attn=[], loss=None, tile_gap=[])
     for b, r in enumerate(roots):
         end = N if b == B - 1 else roots[b + 1]
-        h, probs, top = encode(sd, x[r:end], layers, heads)
+        h, probs, top, gaps = encode(sd, x[r:end], layers, heads)
+        res.tile_gap.append(gaps)   # [tree][layer] -> [n], head 0
         res.hidden[r:end] = h
         # attention_head.sum(-2).sum(1) per layer (explain_PHEME.py:590), summed over the layers
         res.attn_sum[r:end] = sum(P.sum(-2).sum(0) for P in probs)
@@ -146,6 +163,40 @@ CASES = {
     # overflows fp32 without the max subtraction.  Head 1 keeps the spread condition's soft rows.
     "sharp": dict(_SMALL, intermediate=128, layers=1, lengths=[12, 24], qk_factor=4.0),
 }
+# ---- the edge cases of tests/test_gpu_bert_edges.py: shapes and paths the table above does not
+# reach.  Each entry carries its own seed (case() derives a seed from the name's position in
+# sorted(CASES), so CASES itself must not grow).  The seeds, weight_factor and qk_factor are chosen so
+# that tests/test_bert.py's conditions hold at their limits (feasibility 1e-5, 5 % left out, spread,
+# prediction gap, sharp_tiles' cross-tile gaps).
+_LENGTHS_5 = [2, 5, 1, 9, 3]
+EDGE_CASES = {
+    # B = 300 > 256: the second iteration of the setup's loops over B; roots, head and finish at B = 300
+    "many_trees": dict(_SMALL, hidden=64, intermediate=64, layers=1, lengths=[1 + b % 3 for b in range(300)],
+                       first=3, seed=251),
+    # 3 heads and query tiles 0 .. 2: the partial column sums' [qt][head][row] index
+    "heads3_tiles": dict(_SMALL, hidden=192, intermediate=192, lengths=[70, 33, 1, 96], weight_factor=4.0, seed=202),
+    # head 0's scores spread until the largest of a later key tile is more than 10 above (and, in other
+    # rows, below) the first tile's: the running maximum's and sum's rescale across key tiles
+    "sharp_tiles": dict(_SMALL, intermediate=128, layers=1, lengths=[70, 100], weight_factor=1.5, qk_factor=16.0,
+                        seed=203),
+    # kMaxHidden: 16 values per lane in ln_row, 16 heads, the head's whole pooled[] array
+    "hidden_1024": dict(_SMALL, hidden=1024, intermediate=64, layers=1, lengths=[5, 40], weight_factor=2.0, seed=204),
+    # 5 heads (odd per); the head's dot product has a partly active second iteration; the largest intermediate
+    "hidden_320": dict(_SMALL, hidden=320, intermediate=4096, layers=1, lengths=[3, 34], weight_factor=3.0, seed=205),
+    # every slot of bgcn_bert_args::layer; attn_sum accumulated 24 times
+    "layers_24": dict(_SMALL, hidden=64, intermediate=64, layers=24, lengths=[1, 9, 33], weight_factor=2.0, seed=206),
+    # the head's class loop over the four waves, seq_head_tail at 1, 63 and 64 lanes
+    "classes_1": dict(_SMALL, out=1, lengths=_LENGTHS_5, seed=207),
+    "classes_63": dict(_SMALL, out=63, lengths=_LENGTHS_5, seed=208),
+    "classes_64": dict(_SMALL, out=64, lengths=_LENGTHS_5, seed=209),
+    # every grid is sized from max_pos: not a multiple of 32 or 256, and the cap at a max_pos other than 512
+    "short_pos": dict(_SMALL, max_pos=40, lengths=[40, 39, 8], seed=210),
+    # N = 8217 >= kX6MinRows: every full-form GEMM on the six-product bf16-MFMA kernel; the root-only
+    # form of the same batch (127 rows) stays on the exact-fp32 one
+    "rows_over_switch": dict(_SMALL, intermediate=128, layers=1, lengths=[65] * 126 + [27], seed=211),
+}
+PRED_GAP = 2e-4    # the oracle's top-1 to top-2 logp gap of every edge-case tree exceeds this: twice the GPU bar
+TILE_GAP = 10.0    # sharp_tiles: rows whose later tiles lead the first by more than this, and rows the other way
 RANK_GAP = 2e-4    # positions whose oracle value is closer than this to a neighbour's are not compared
 RANK_SKIP = 0.05   # at most this share of a case's positions may be left out that way
 
@@ -175,6 +226,21 @@ def _make(name, c, seed):
 def case(name):
     """The seeded inputs of a case and its fp64 oracle, computed once and shared (read-only)."""
     return _make(name, CASES[name], sorted(CASES).index(name) + 1)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(name):
+    """As case(), for EDGE_CASES and the entry's own seed."""
+    c = EDGE_CASES[name]
+    return _make(name, c, c["seed"])
+
+
+def pred_gap(logp):
+    """The smallest top-1 to top-2 gap of ``logp [B, C]`` over the trees (inf for one class)."""
+    if logp.size(1) < 2:
+        return float("inf")
+    top = logp.topk(2, dim=1).values
+    return float((top[:, 0] - top[:, 1]).min())
 
 
 def model_for(c, device=None):

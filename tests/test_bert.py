@@ -3,7 +3,9 @@ tests/bert_ref.py is what ``transformers``' ``BertModel`` computes, the module's
 reference's key for key, the C ABI and its ctypes mirror agree, the entry point rejects bad arguments
 before any device work, and the conditions the GPU tests lean on hold in the oracle alone (the class
 reads the root row only, attention is neither uniform nor one-hot, the rankings' gaps, and torch's
-own fp32 sits 10x under the GPU tests' 1e-4 bar)."""
+own fp32 sits 10x under the GPU tests' 1e-4 bar), over the cases of test_gpu_bert.py and the edge
+cases of test_gpu_bert_edges.py alike (plus the edge cases' own: prediction gaps, sharp_tiles' cross-tile
+score gaps)."""
 import ctypes
 import os
 import shutil
@@ -17,6 +19,8 @@ import bert_ref as R
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "bgcn.h")
 ALL = sorted(R.CASES)
+EDGES = sorted(R.EDGE_CASES)
+INTERNAL = os.path.join(ROOT, "bigcn_amd", "csrc", "bgcn_internal.h")
 # worst |restatement - transformers| in fp64 over the cases, measured when this test was written:
 # last_hidden_state 6.4e-15, pooler_output 4.0e-15, summed attentions 1.4e-14.  The bar is 100x the worst.
 TRANSFORMERS_BAR = 100 * 1.4e-14
@@ -225,10 +229,14 @@ def test_bad_arguments_fail_before_any_device_work():
     rejected(plausible(), b"16-byte", fake + 0x1000004, 1 << 30)
 
 
-@pytest.mark.parametrize("name", ALL)
+def _case(name):
+    return R.case(name) if name in R.CASES else R.edge_case(name)
+
+
+@pytest.mark.parametrize("name", ALL + EDGES)
 def test_the_class_reads_the_root_row_only(name):
     """Replacing every non-root row leaves the oracle's logp exactly unchanged."""
-    c = R.case(name)
+    c = _case(name)
     x = torch.randn(c.x.shape, generator=torch.Generator().manual_seed(77)) * 3.0
     x[c.rootindex] = c.x[c.rootindex]
     got = R.run(c.sd, x, c.rootindex, c.cfg["layers"], c.heads, c.y)
@@ -252,22 +260,23 @@ def test_cases_are_the_table():
     assert R.case("sharp").ref.top_score > 88.0     # exp(88.8) overflows fp32
 
 
-@pytest.mark.parametrize("name", [n for n in ALL if n not in ("single", "many")])
+@pytest.mark.parametrize("name", [n for n in ALL if n not in ("single", "many")] +
+                         ["heads3_tiles", "sharp_tiles", "short_pos", "hidden_1024", "rows_over_switch"])
 def test_attention_is_neither_uniform_nor_one_hot(name):
     """The spread condition: among the oracle's attention rows with at least 8 keys there are rows
     whose largest probability is above 0.5 and rows where it is below."""
-    rm = R.case(name).ref.row_max
+    rm = _case(name).ref.row_max
     hi, lo = int((rm > 0.5).sum()), int((rm < 0.5).sum())
     print(name, "rows", rm.numel(), "above", hi, "below", lo)
     assert hi > 0 and lo > 0
 
 
-@pytest.mark.parametrize("name", ALL)
+@pytest.mark.parametrize("name", ALL + EDGES)
 def test_the_bar_is_feasible(name):
     """Torch's own fp32 CPU evaluation of the restatement is within 1e-5 of the fp64 oracle on hidden,
     hidden_sum / hidden, logp and the loss, and within 1e-5 max(1, |ref|) on attn_sum, for every GPU
     case at its recorded weight_factor: the arithmetic alone sits 10x under the GPU tests' 1e-4 bar."""
-    c = R.case(name)
+    c = _case(name)
     got = R.run(c.sd, c.x, c.rootindex, c.cfg["layers"], c.heads, c.y, dtype=torch.float32)
     errs = {"hidden": float((got.hidden.double() - c.ref.hidden).abs().max()),
             "hidden_sum/hidden": float((got.hidden_sum.double() - c.ref.hidden_sum).abs().max()) / c.cfg["hidden"],
@@ -278,11 +287,11 @@ def test_the_bar_is_feasible(name):
     assert max(errs.values()) <= 1e-5, errs
 
 
-@pytest.mark.parametrize("name", ALL)
+@pytest.mark.parametrize("name", ALL + EDGES)
 def test_rankings_leave_few_positions_out(name):
     """A condition on the inputs (the seeds): at most 5 % of a case's ranking positions lie within 2e-4
     of a neighbour in the oracle's sorted values, where the GPU test does not compare the order."""
-    c = R.case(name)
+    c = _case(name)
     out = total = 0
     for lst in (c.ref.rank_hidden, c.ref.rank_attn):
         for _, v in lst:
@@ -291,3 +300,66 @@ def test_rankings_leave_few_positions_out(name):
             total += ok.numel()
     print(name, "left out", out, "of", total)
     assert out <= R.RANK_SKIP * total
+
+
+def test_edge_cases_are_the_table():
+    """N, B, heads and the size each edge case exists for, the limits read from the sources."""
+    import re
+    from bigcn_amd import _lib
+    assert EDGES == ["classes_1", "classes_63", "classes_64", "heads3_tiles", "hidden_1024", "hidden_320", "layers_24",
+                     "many_trees", "rows_over_switch", "sharp_tiles", "short_pos"]
+    assert len({c["seed"] for c in R.EDGE_CASES.values()}) == len(EDGES)
+    table = {"many_trees": (603, 300, 1), "heads3_tiles": (200, 4, 3), "sharp_tiles": (170, 2, 2),
+             "hidden_1024": (45, 2, 16), "hidden_320": (37, 2, 5), "layers_24": (43, 3, 1), "classes_1": (20, 5, 2),
+             "classes_63": (20, 5, 2), "classes_64": (20, 5, 2), "short_pos": (87, 3, 2),
+             "rows_over_switch": (8217, 127, 2)}
+    for name, want in table.items():
+        c = R.edge_case(name)
+        assert (c.N, c.B, c.heads) == want, name
+    cfg = R.EDGE_CASES
+    c = R.edge_case("many_trees")
+    assert c.B > 256 and c.first == 3 and set(cfg["many_trees"]["lengths"]) == {1, 2, 3}     # k_bert_setup's stride
+    assert cfg["heads3_tiles"]["lengths"] == [70, 33, 1, 96] and (96 - 1) // R.QUERY_TILE == 2
+    assert cfg["sharp_tiles"]["lengths"] == [70, 100] and cfg["sharp_tiles"]["qk_factor"] > 1
+    bert = open(os.path.join(ROOT, "bigcn_amd", "csrc", "bgcn_bert.hip")).read()
+    assert cfg["hidden_1024"]["hidden"] == int(re.search(r"kMaxHidden = (\d+);", bert).group(1))
+    assert cfg["hidden_320"]["hidden"] % 256 == 64 and cfg["hidden_320"]["intermediate"] == 4096
+    assert _lib.load_library().bgcn_bert_workspace_size(37, 2, 320, 4096 + 64, 1, 1) == 0    # 4096 is the largest
+    assert cfg["layers_24"]["layers"] == _lib.BGCN_BERT_MAX_LAYERS
+    assert int(re.search(r"#define BGCN_BERT_MAX_LAYERS (\d+)", open(HEADER).read()).group(1)) == 24
+    lstm_h = open(os.path.join(ROOT, "bigcn_amd", "csrc", "bgcn_lstm.h")).read()
+    assert cfg["classes_64"]["out"] == int(re.search(r"kMaxOut = (\d+);", lstm_h).group(1))
+    assert (cfg["classes_1"]["out"], cfg["classes_63"]["out"]) == (1, 63)
+    c = R.edge_case("short_pos")
+    assert c.cfg["max_pos"] == 40 == max(c.cfg["lengths"]) and 40 % 32 and c.sd[
+        "BERT.embeddings.position_embeddings.weight"].size(0) == 40
+    x6 = int(re.search(r"kX6MinRows = (\d+);", open(INTERNAL).read()).group(1))
+    c = R.edge_case("rows_over_switch")
+    assert c.N >= x6 > c.B and c.cfg["hidden"] % 128 == 0 and c.cfg["intermediate"] % 128 == 0
+    under = [n for n in ALL + EDGES if n != "rows_over_switch"]
+    assert all(_case(n).N < x6 for n in under)         # every other case runs the exact-fp32 GEMM alone
+
+
+@pytest.mark.parametrize("name", EDGES)
+def test_predictions_have_a_margin(name):
+    """A condition on the inputs: the oracle's smallest top-1 to top-2 gap in logp over the trees is
+    above 2e-4, twice the GPU bar, so a GPU logp inside the bar has the oracle's argmax and the GPU
+    tests may assert ``pred`` equal."""
+    gap = R.pred_gap(R.edge_case(name).ref.logp)
+    print(name, "smallest gap", gap)
+    assert gap > R.PRED_GAP
+
+
+def test_sharp_tiles_crosses_key_tiles_both_ways():
+    """The rows at positions >= 64 of head 0 (three key tiles): there are rows whose largest score
+    sits in a later key tile, more than 10 above the first tile's largest (the running maximum moves
+    and the sum so far shrinks by e^-10 or more), and rows where the first tile's largest is more than
+    10 above every later key's.  A missing or misplaced rescale factor is then wrong by e^10.  The
+    largest score passes +-88 as well: exp overflows fp32 without the max subtraction."""
+    c = R.edge_case("sharp_tiles")
+    gap = torch.cat([layers[0][64:] for layers in c.ref.tile_gap])
+    later, first = int((gap > R.TILE_GAP).sum()), int((gap < -R.TILE_GAP).sum())
+    print("rows", gap.numel(), "later tile leads", later, "first tile leads", first, "top score", c.ref.top_score)
+    assert gap.numel() == 6 + 36 and not bool(torch.isnan(gap).any())
+    assert later > 0 and first > 0
+    assert c.ref.top_score > 88.0

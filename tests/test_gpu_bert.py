@@ -6,7 +6,6 @@ determinism, independence of the workspace's and the output buffers' prior conte
 Bars: hidden, hidden_sum / hidden (the row sum divided by the hidden width: the row's mean) and logp
 within 1e-4 absolute of the oracle, the project's fp32 bar; attn_sum within 1e-4 max(1, |ref|).
 With BGCN_BERT_PARITY_OUT set, the parity test writes every case's worst errors to that JSON."""
-import functools
 import json
 import os
 from types import SimpleNamespace
@@ -15,43 +14,11 @@ import pytest
 import torch
 
 import bert_ref as R
+from bert_gpu_util import BAR, DEV, _check_rankings, _data, _err, _inputs, _model, _parity_errors
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-BAR = 1e-4
 ALL = sorted(R.CASES)
 _parity = {}
-
-
-@functools.lru_cache(maxsize=None)
-def _model(name):
-    return R.model_for(R.case(name), DEV)
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(name):
-    c = R.case(name)
-    wide = c.x._base if c.x._base is not None else c.x
-    x = wide.to(DEV)[:, :c.cfg["hidden"]]       # the case's row stride survives the copy
-    return x, c.rootindex.to(DEV), c.y.to(DEV)
-
-
-def _data(name, T=3, drop_first=False):
-    """A PyG-like batch whose ``x [N, T * hidden]`` max-pools over T to the case's rows.  ``drop_first``:
-    without the rows above the first tree, which a PyG batch vector cannot name."""
-    c = R.case(name)
-    x, root, y = _inputs(name)
-    if drop_first and c.first:
-        d = _data(name, T)
-        return SimpleNamespace(x=d.x[c.first:], rootindex=root - c.first, y=y, batch=c.batch.to(DEV))
-    g = torch.Generator().manual_seed(5)
-    lower = x.unsqueeze(1) - torch.rand(c.N, T - 1, c.cfg["hidden"], generator=g).to(DEV)
-    wide = torch.cat((lower[:, :1], x.unsqueeze(1), lower[:, 1:]), 1).reshape(c.N, -1).contiguous()
-    return SimpleNamespace(x=wide, rootindex=root, y=y, batch=c.batch.to(DEV))
-
-
-def _err(got, want):
-    return float((got.double().cpu() - want).abs().max())
 
 
 @pytest.mark.parametrize("name", ALL)
@@ -62,9 +29,7 @@ def test_parity_with_the_fp64_oracle(name):
     logp, hidden, (hsum, asum) = m.forward_batch(x, root, return_hidden=True, return_sums=True)
     m.check_status()
     ref = c.ref
-    errs = {"logp_root_only": _err(logp_root, ref.logp), "logp_full": _err(logp, ref.logp),
-            "hidden": _err(hidden, ref.hidden), "hidden_sum/hidden": _err(hsum, ref.hidden_sum) / c.cfg["hidden"],
-            "attn_sum": float(((asum.double().cpu() - ref.attn_sum).abs() / ref.attn_sum.abs().clamp(min=1)).max())}
+    errs = _parity_errors(c, logp_root, logp, hidden, hsum, asum)
     print(name, {k: f"{v:.3e}" for k, v in errs.items()})
     _parity[name] = {"errors": errs, "margins": {k: BAR / max(v, 1e-300) for k, v in errs.items()},
                      "N": c.N, "B": c.B, "top_score": ref.top_score}
@@ -225,16 +190,4 @@ def test_explain_rankings(name):
     import bigcn_amd
     c, m = R.case(name), _model(name)
     res = bigcn_amd.explain(m, _data(name, drop_first=True))
-    assert torch.equal(res.prediction.cpu(), c.ref.pred)
-    roots = [r - c.first for r in c.rootindex.tolist() + [c.N]]
-    for what, order, srt, ranks, scale in (("hidden", res.hidden_order, res.hidden_sorted, c.ref.rank_hidden, c.cfg["hidden"]),
-                                           ("attn", res.attn_order, res.attn_sorted, c.ref.rank_attn, None)):
-        for b, (o_ref, v_ref) in enumerate(ranks):
-            a, e = roots[b], roots[b + 1]
-            v = srt[a:e].double().cpu()
-            tol = (BAR * scale) if scale else BAR * v_ref.abs().clamp(min=1)
-            assert bool(((v - v_ref).abs() <= tol).all()), (what, b)
-            ok = R.rank_compared(v_ref)
-            assert torch.equal(order[a:e].cpu().long()[ok], o_ref[ok]), (what, b)
-    rec = res.to_reference_dict(c.B - 1)
-    assert len(rec["bert_attentions_top_k"][0]) == c.cfg["lengths"][-1] and rec["prediction"] == int(c.ref.pred[-1])
+    _check_rankings(c, res)
