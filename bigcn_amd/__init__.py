@@ -34,6 +34,10 @@ Drop-in symbols for the reference's hot path (cwkd/BiGCN):
   class depends on each tree's first row only, so ``evaluate`` / ``validate`` are a chain of
   ``[B, hidden]`` GEMMs (``bgcn_bert_eval``, root-only form); ``explain_batch`` runs the full causal
   encoder with a two-pass MFMA attention kernel and ranks the hidden and attention sums per tree
+* ``TreeBERTTrainStep`` / ``bert_adam`` - the BERT baseline's training-loop body (BERT_Twitter.py:89-119):
+  the forward with ``BertModel``'s four dropout sites, the loss and the backward on the trees' root rows
+  as one native call (``bgcn_bert_train_grad``, also ``TreeBERT.grad_batch``), then the reference's Adam
+  as ``MultiAdam`` launches over slices of 128 tensors
 * ``FusedTrainStep`` - the training-loop body (BiGCN_Twitter.py:183-189) as one native call
   + the data-parallel all-reduce + fused Adam
 
@@ -45,7 +49,7 @@ from .compare import compare, rank_similarity, tree_centrality
 from .ebgcn import EBGCN
 from .explain import explain, segment_rank
 from .lstm import LSTM, LSTMTrainStep, lstm_adam
-from .bert import TreeBERT
+from .bert import TreeBERT, TreeBERTTrainStep, bert_adam
 from . import metrics
 from .metrics import EpochMetrics, class_metrics, confusion, evaluation4class, evaluationclass
 from .ops import (Graph, bigcn_encoder, build_graph, ebgcn_conv2_lin_train, edge_infer, edge_infer_train,
@@ -61,6 +65,6 @@ __all__ = ["GCNConv", "scatter_mean", "TDrumorGCN", "BUrumorGCN", "BiGCN", "Net"
            "MultiAdam", "ebgcn_adam", "EBGCNTrainStep", "drop_edges",
            "explain", "segment_rank",
            "compare", "tree_centrality", "rank_similarity",
-           "LSTM", "LSTMTrainStep", "lstm_adam", "TreeBERT",
+           "LSTM", "LSTMTrainStep", "lstm_adam", "TreeBERT", "TreeBERTTrainStep", "bert_adam",
            "metrics", "confusion", "class_metrics", "evaluation4class", "evaluationclass", "EpochMetrics"]
 __version__ = "0.1.0"

@@ -75,7 +75,7 @@ EXPORTED_SYMBOLS = (
     "bgcn_ebgcn_conv2_lin_train_workspace_size", "bgcn_ebgcn_conv2_lin_train_fwd", "bgcn_ebgcn_conv2_lin_train_bwd",
     "bgcn_adam_multi_table_size", "bgcn_adam_multi_plan", "bgcn_adam_multi_step", "bgcn_ebgcn_train_loss",
     "bgcn_lstm_workspace_size", "bgcn_lstm_eval", "bgcn_lstm_train_workspace_size", "bgcn_lstm_train_grad",
-    "bgcn_bert_workspace_size", "bgcn_bert_eval",
+    "bgcn_bert_workspace_size", "bgcn_bert_eval", "bgcn_bert_train_workspace_size", "bgcn_bert_train_grad",
 )
 
 BGCN_ADAM_MULTI_MAX_TENSORS = 128
@@ -238,6 +238,19 @@ class BertArgs(Structure):
         ("pooler_w", c_void_p), ("pooler_b", c_void_p), ("fc_w", c_void_p), ("fc_b", c_void_p), ("y", c_void_p),
         ("logp", c_void_p), ("loss", c_void_p), ("correct", c_void_p), ("pred", c_void_p),
         ("hidden_out", c_void_p), ("hidden_sum", c_void_p), ("attn_sum", c_void_p), ("status", c_void_p),
+    ]
+
+
+class BertTrainArgs(Structure):
+    """bgcn_bert_train_args (include/bgcn.h): ``fwd``, one gradient pointer per weight pointer of
+    ``fwd`` (the eight top-level ones, then ``d_layer``), ``dx``, the skip flag and the dropout draw."""
+    _fields_ = [
+        ("fwd", BertArgs),
+        ("d_pos_emb", c_void_p), ("d_type_emb", c_void_p), ("d_emb_ln_w", c_void_p), ("d_emb_ln_b", c_void_p),
+        ("d_pooler_w", c_void_p), ("d_pooler_b", c_void_p), ("d_fc_w", c_void_p), ("d_fc_b", c_void_p),
+        ("d_layer", BertLayer * BGCN_BERT_MAX_LAYERS),
+        ("dx", c_void_p), ("skip_flag", c_void_p), ("drop_seed", c_uint64),
+        ("hidden_dropout", c_float), ("attn_dropout", c_float),
     ]
 
 
@@ -412,6 +425,8 @@ _SIGS = {
     "bgcn_lstm_train_grad": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_bert_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int]),
     "bgcn_bert_eval": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "bgcn_bert_train_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64]),
+    "bgcn_bert_train_grad": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

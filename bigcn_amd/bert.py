@@ -1,5 +1,5 @@
-"""The TreeBERT baseline of the PHEME comparison (``model/Twitter/BERT_Twitter.py``), evaluation and
-explain.
+"""The TreeBERT baseline of the PHEME comparison (``model/Twitter/BERT_Twitter.py``): evaluation,
+explain and training.
 
 ``TreeBERT`` holds the reference's parameters key for key (``BERT.embeddings...``, ``BERT.encoder.
 layer.{i}...``, ``BERT.pooler.dense.*``, ``fc.*``: ``BertModel``'s names and shapes), so a
@@ -15,7 +15,17 @@ GEMMs with no q, k or score work.  The explain run needs every row (``last_hidde
 attention probabilities): :meth:`TreeBERT.explain_batch` and ``forward_batch(..., return_hidden /
 return_sums)`` run the *full* form, the causal encoder over all rows.
 
-Evaluation only: the per-tree ``forward`` raises in training mode (no autograd path, no dropout).
+Training: the loss is a function of each tree's first row in training mode too (dropout is
+element-wise and cannot couple rows; the gradient of a softmax over one unmasked key is exactly 0),
+so :meth:`TreeBERT.grad_batch` - the loop body's forward, loss and backward (``BERT_Twitter.py:89-119``)
+for a whole batch as one native call, ``bgcn_bert_train_grad`` - is a chain of ``[B, hidden]`` GEMMs
+with ``BertModel``'s four dropout sites drawn from a counter-based hash of ``(drop_seed, site, tree,
+column or head)``.  The query / key parameters get exact-zero gradients (zeros, not ``None``: the
+reference's Adam still decays them), ``position_embeddings`` and ``token_type_embeddings`` a gradient
+in row 0 only, ``word_embeddings`` none.  :class:`TreeBERTTrainStep` adds the reference's Adam
+(:func:`bert_adam`: BERT-base's 200 tensors as consecutive :class:`MultiAdam` slices) with no host
+sync.  The per-tree ``forward`` stays an evaluation call and raises in training mode: there is no
+autograd path through it.
 """
 from __future__ import annotations
 
@@ -25,7 +35,8 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from ._lib import check, ptr, stream_handle
+from ._lib import check, ptr, raise_on_status, stream_handle
+from .optim import MULTI_MAX_TENSORS, MultiAdam
 
 _LAYER_FIELDS = (("q_w", "attention.self.query.weight"), ("q_b", "attention.self.query.bias"),
                  ("k_w", "attention.self.key.weight"), ("k_b", "attention.self.key.bias"),
@@ -99,23 +110,28 @@ class BertExplanation:
 
 
 class TreeBERT(torch.nn.Module):
-    """Drop-in for the reference's ``TreeBERT`` (``BERT_Twitter.py:20-42``) in eval mode.
+    """Drop-in for the reference's ``TreeBERT`` (``BERT_Twitter.py:20-42``) in eval mode; training goes
+    through :meth:`grad_batch` / :class:`TreeBERTTrainStep`.
 
     The positional signature is the reference's, which ignores ``in_feats``, ``hid_feats`` and
     ``out_feats`` (they are stored): its encoder is BERT-base and its head ``Linear(768, 4)``.  The
     keywords give the encoder's sizes (defaults: BERT-base) and ``num_classes`` the head's width, so
     the default module has exactly the reference's ``state_dict``.  Initialisation is BERT's: normal
-    with std 0.02, LayerNorm weights 1 and biases 0, every other bias 0.
+    with std 0.02, LayerNorm weights 1 and biases 0, every other bias 0.  ``hidden_dropout`` and
+    ``attn_dropout`` (``BertConfig``'s 0.1 defaults) are used by training only and are no part of the
+    ``state_dict``.
 
     ``forward(data)`` is the reference's per-tree call; :meth:`forward_batch`, :meth:`evaluate`,
     :meth:`validate` and :meth:`explain_batch` run a whole batch of trees per native call."""
 
     def __init__(self, in_feats=256 * 768, hid_feats=64, out_feats=64, device=None, pooling='max', version=0, *,
-                 hidden=768, heads=12, intermediate=3072, num_layers=12, max_pos=512, vocab=30522, num_classes=4):
+                 hidden=768, heads=12, intermediate=3072, num_layers=12, max_pos=512, vocab=30522, num_classes=4,
+                 hidden_dropout=0.1, attn_dropout=0.1):
         super().__init__()
         self.in_feats, self.hid_feats, self.out_feats = in_feats, hid_feats, out_feats
         self.hidden, self.heads, self.intermediate, self.num_layers = hidden, heads, intermediate, num_layers
         self.max_pos = max_pos
+        self.hidden_dropout, self.attn_dropout = float(hidden_dropout), float(attn_dropout)
         self.BERT = _bert_holders(hidden, intermediate, num_layers, max_pos, vocab)
         self.fc = torch.nn.Linear(hidden, num_classes)
         with torch.no_grad():
@@ -240,6 +256,86 @@ class TreeBERT(torch.nn.Module):
         st["seen"].bitwise_or_(st["status"])   # the call zeroes its status word; check_status reads this one
         return r
 
+    def _train(self, x, rootindex, y, dx=False, grads=None, want_pred=False, skip_flag=None, drop_seed=0,
+               hidden_dropout=None, attn_dropout=None):
+        """One ``bgcn_bert_train_grad`` call.  ``grads``: fp32 contiguous buffers in :meth:`names` order
+        (default: new ones)."""
+        if not x.is_cuda:
+            raise _lib.BGCNError("bigcn_amd ops take device tensors (no CPU path)")
+        if x.dim() != 2 or x.size(1) != self.hidden:
+            raise ValueError(f"the sequences' rows must be [N, {self.hidden}], got {tuple(x.shape)}")
+        dev = x.device
+        st = self._bind(dev)
+        if not (x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+                and x.stride(0) >= x.size(1)):
+            x = x.float().contiguous()
+        rootindex = rootindex.to(device=dev, dtype=torch.int64).contiguous()
+        N, B, C = int(x.size(0)), int(rootindex.numel()), self.num_classes
+        if N < 1 or B < 1:
+            raise ValueError("the batch needs at least one row and one tree")
+        y = y.to(device=dev, dtype=torch.int64).contiguous()
+        if y.numel() != B:
+            raise ValueError("y must have one label per tree")
+        if st["sizes"].get("train") != B:
+            need = _lib.lib().bgcn_bert_train_workspace_size(N, B, self.hidden, self.intermediate, self.num_layers)
+            if need == 0:
+                raise _lib.BGCNError("bgcn_bert_train_grad: unsupported shape (hidden = 64 heads in [64, 1024], "
+                                     "intermediate % 64 in [64, 4096], num_layers in [1, 24])")
+            if st["ws"].get("train") is None or st["ws"]["train"].numel() < need or st["ws"]["train"].device != dev:
+                st["ws"]["train"] = _lib.workspace(need, dev)
+            st["sizes"]["train"] = B
+        ws = st["ws"]["train"]
+        r = {"logp": torch.empty(B, C, dtype=torch.float32, device=dev),
+             "loss": torch.empty(1, dtype=torch.float32, device=dev),
+             "correct": torch.empty(1, dtype=torch.int32, device=dev),
+             "pred": torch.empty(B, dtype=torch.int64, device=dev) if want_pred else None}
+        ta = st.get("targs")
+        if ta is None:
+            ta = st["targs"] = _lib.BertTrainArgs()
+        ctypes.memmove(ctypes.addressof(ta.fwd), ctypes.addressof(st["args"]), ctypes.sizeof(_lib.BertArgs))
+        a = ta.fwd
+        a.x, a.ldx, a.num_nodes = x.data_ptr(), x.stride(0), N
+        a.seq_start, a.num_seqs = rootindex.data_ptr(), B
+        a.y, a.logp, a.loss, a.correct, a.pred = y.data_ptr(), r["logp"].data_ptr(), r["loss"].data_ptr(), \
+            r["correct"].data_ptr(), ptr(r["pred"])
+        a.hidden_out = a.hidden_sum = a.attn_sum = None
+        if grads is None:
+            by_name = dict(self.named_parameters())
+            grads = [torch.empty(by_name[n].shape, dtype=torch.float32, device=dev) for n in self.names()]
+        if skip_flag is None:
+            skip_flag = torch.empty(1, dtype=torch.float32, device=dev)
+        gx = torch.empty(N, x.stride(0), dtype=torch.float32, device=dev) if dx else None
+        it = iter(grads)
+        for field, _ in _TOP_FIELDS:
+            setattr(ta, "d_" + field, next(it).data_ptr())
+        for i in range(self.num_layers):
+            for field, _ in _LAYER_FIELDS:
+                setattr(ta.d_layer[i], field, next(it).data_ptr())
+        ta.dx, ta.skip_flag, ta.drop_seed = ptr(gx), skip_flag.data_ptr(), int(drop_seed) & (2 ** 64 - 1)
+        ta.hidden_dropout = self.hidden_dropout if hidden_dropout is None else float(hidden_dropout)
+        ta.attn_dropout = self.attn_dropout if attn_dropout is None else float(attn_dropout)
+        check(_lib.lib().bgcn_bert_train_grad(ctypes.addressof(ta), ptr(ws), ws.numel(), stream_handle()))
+        st["seen"].bitwise_or_(st["status"])
+        r.update(grads=grads, dx=None if gx is None else gx[:, :self.hidden], skip_flag=skip_flag)
+        return r
+
+    def grad_batch(self, x, rootindex, y, dx=False, drop_seed=0, hidden_dropout=None, attn_dropout=None):
+        """Forward in training mode, mean NLL loss and backward of one batch of trees
+        (``BERT_Twitter.py:89-119`` up to ``optimizer.step()``) as one native call: ``(loss, correct,
+        grads)``, 0-dim fp32 / int32 device tensors and a dict of the loss's gradients keyed by the
+        ``state_dict`` names - every name of :meth:`names` (zeros for the query / key tensors and for
+        the rows past the first of both embeddings), no ``word_embeddings`` entry - plus ``"x"`` (``[N,
+        hidden]``: the root rows' gradient, zeros elsewhere) with ``dx=True``.  Only the trees' first
+        rows of ``x`` are read.  The dropout masks are a function of ``drop_seed``; the rates default
+        to the module's.  New tensors on every call; ``.grad`` is not touched; no host sync.  Validity:
+        :meth:`check_status`; the gradients of a flagged batch are not to be used."""
+        r = self._train(x, rootindex, y, dx=dx, drop_seed=drop_seed, hidden_dropout=hidden_dropout,
+                        attn_dropout=attn_dropout)
+        grads = dict(zip(self.names(), r["grads"]))
+        if dx:
+            grads["x"] = r["dx"]
+        return r["loss"].view(()), r["correct"].view(()), grads
+
     def forward(self, data):
         """The reference's per-tree call, on the root-only form (no host sync).  ``version != 2``:
         ``data [n, T, hidden]`` is pooled over ``T`` and run as one sequence of ``n`` rows, giving
@@ -247,7 +343,8 @@ class TreeBERT(torch.nn.Module):
         sequences of ``T`` tokens, giving ``[n, num_classes]``."""
         if self.training:
             raise NotImplementedError("bigcn_amd.TreeBERT.forward is the per-tree evaluation call and has no autograd "
-                                      "path: training TreeBERT is not implemented here, call model.eval()")
+                                      "path: for training use bigcn_amd.TreeBERTTrainStep(model).step(batch) (or "
+                                      "TreeBERT.grad_batch), else call model.eval()")
         if data.dim() != 3:
             raise ValueError(f"data must be [n, T, {self.hidden}], got {tuple(data.shape)}")
         if self.version == 2:
@@ -353,3 +450,138 @@ class TreeBERT(torch.nn.Module):
         if s & _lib.BGCN_STATUS_SEQUENCE:
             raise IndexError("the batch holds a rootindex that does not increase strictly or is out of range, "
                              "a tree longer than max_pos, or a label outside [0, num_classes)")
+
+
+class ChunkedAdam:
+    """What :func:`bert_adam` returns: :class:`MultiAdam`'s step over more tensors than one
+    ``MultiAdam`` takes, as ``ceil(n / 128)`` of them over consecutive slices of the parameter list,
+    one launch each.  Only the first slice is given ``skip_count``, so a skipped step counts once."""
+
+    def __init__(self, params, lr: float, weight_decay: float):
+        params = list(params)
+        self.chunks = [MultiAdam([{"params": params[i:i + MULTI_MAX_TENSORS]}], lr=lr, weight_decay=weight_decay)
+                       for i in range(0, len(params), MULTI_MAX_TENSORS)]
+
+    def params(self):
+        return [p for c in self.chunks for p in c.params()]
+
+    @property
+    def step_count(self) -> int:
+        return self.chunks[0].step_count if self.chunks else 0
+
+    def step(self, grads=None, skip_flag=None, skip_count=None) -> None:
+        """``grads``: one entry per parameter in :meth:`params` order (``None`` allowed: that parameter is
+        left alone), default ``p.grad``; ``skip_flag`` / ``skip_count`` as :meth:`MultiAdam.step`."""
+        if grads is not None and len(grads) != len(self.params()):
+            raise ValueError("grads must have one entry per parameter")
+        k = 0
+        for i, c in enumerate(self.chunks):
+            n = len(c.params())
+            c.step(grads=None if grads is None else grads[k:k + n], skip_flag=skip_flag,
+                   skip_count=skip_count if i == 0 else None)
+            k += n
+
+    def state_dict(self) -> dict:
+        """``step_count`` and, in :meth:`params` order, copies of both moments."""
+        ps = self.params()
+        state = {p: c.state[p] for c in self.chunks for p in c.params()}
+        return {"step_count": self.step_count, "exp_avg": [state[p][0].clone() for p in ps],
+                "exp_avg_sq": [state[p][1].clone() for p in ps]}
+
+    def load_state_dict(self, sd: dict) -> None:
+        ps = self.params()
+        if len(sd["exp_avg"]) != len(ps) or len(sd["exp_avg_sq"]) != len(ps):
+            raise ValueError("the state holds another number of tensors")
+        state = {p: c.state[p] for c in self.chunks for p in c.params()}
+        with torch.no_grad():
+            for p, m, v in zip(ps, sd["exp_avg"], sd["exp_avg_sq"]):
+                state[p][0].copy_(m)
+                state[p][1].copy_(v)
+        for c in self.chunks:
+            c.step_count = int(sd["step_count"])
+
+
+def bert_adam(model, lr: float = 5e-4, weight_decay: float = 1e-4) -> ChunkedAdam:
+    """The reference's optimiser (``BERT_Twitter.py``: ``Adam(model.parameters(), lr=5e-4,
+    weight_decay=1e-4)``) over all of ``model.parameters()`` in their order.  ``word_embeddings`` is
+    in the list and never gets a gradient, so it is left alone, as by torch."""
+    return ChunkedAdam(model.parameters(), lr, weight_decay)
+
+
+class TreeBERTTrainStep:
+    """The body of the reference's training loop (``BERT_Twitter.py:89-119``) for a whole batch with no
+    host sync: the trees' root rows pooled, ``bgcn_bert_train_grad`` (forward with dropout, loss,
+    accuracy, backward into buffers this object owns), then the Adam launches.  The k-th step draws
+    its masks from ``drop_seed + k`` (``drop_seed=None``: drawn once from torch's generator); the seed
+    of the last step is ``last_drop_seed``.  An invalid batch is decided on the device: the call sets
+    the optimiser's ``skip_flag``, the update writes nothing, and :meth:`check_status` reports it with
+    one read.  ``.grad`` is left alone."""
+
+    def __init__(self, model: TreeBERT, optimizer=None, lr: float = 5e-4, weight_decay: float = 1e-4, drop_seed=None):
+        self.model = model
+        self.optimizer = bert_adam(model, lr, weight_decay) if optimizer is None else optimizer
+        self.drop_seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if drop_seed is None else int(drop_seed)
+        self.last_drop_seed = None
+        self.last_skipped = 0
+        self._steps = 0
+        self._st = None
+
+    def _state(self, dev):
+        st = self._st
+        if st is None or st["dev"] != dev:
+            by_name = dict(self.model.named_parameters())
+            st = {"dev": dev, "skip_count": torch.zeros(1, dtype=torch.int32, device=dev),
+                  "skip_flag": torch.zeros(1, dtype=torch.float32, device=dev),
+                  "grads": [torch.zeros(by_name[n].shape, dtype=torch.float32, device=dev)
+                            for n in self.model.names()]}
+            self._st = st
+        return st
+
+    @property
+    def step_count(self) -> int:
+        return self.optimizer.step_count
+
+    def grads(self):
+        """The last step's gradients by ``state_dict`` name (the step's own buffers, overwritten by the next)."""
+        return dict(zip(self.model.names(), self._st["grads"])) if self._st else {}
+
+    def step(self, data, pred: bool = False):
+        """One iteration; ``data`` as :meth:`TreeBERT.evaluate` takes it.  Returns ``(loss, correct)``
+        (0-dim fp32 / int32 device tensors), plus ``pred`` ([B] int64) when ``pred=True``.  An invalid
+        batch skips the update on the device (``step_count`` still advances); :meth:`check_status` tells."""
+        m = self.model
+        if m.version == 2:
+            raise NotImplementedError("TreeBERTTrainStep.step with version == 2: the reference's loop body assigns "
+                                      "the [n, 4] result of an n-node tree into one row of out_labels "
+                                      "(BERT_Twitter.py:103-105), which fails for any tree of more than one node")
+        if not data.x.is_cuda:
+            raise _lib.BGCNError("bigcn_amd ops take device tensors (no CPU path)")
+        st = self._state(data.x.device)
+        self.last_drop_seed = (self.drop_seed + self._steps) & (2 ** 64 - 1)
+        self._steps += 1
+        r = m._train(m._root_rows(data), data.rootindex, data.y, grads=st["grads"], want_pred=pred,
+                     skip_flag=st["skip_flag"], drop_seed=self.last_drop_seed)
+        by_name = dict(m.named_parameters())
+        by_id = {id(by_name[n]): g for n, g in zip(m.names(), st["grads"])}
+        self.optimizer.step(grads=[by_id.get(id(p)) for p in self.optimizer.params()], skip_flag=st["skip_flag"],
+                            skip_count=st["skip_count"])
+        out = (r["loss"].view(()), r["correct"].view(()))
+        return out + (r["pred"],) if pred else out
+
+    def check_status(self) -> int:
+        """One host read: the number of updates skipped since the last check (also in
+        ``last_skipped``), after raising the ``IndexError`` of :meth:`TreeBERT.check_status` when a batch
+        stepped on since then was invalid."""
+        mst = self.model.__dict__.get("_state")
+        if self._st is None or mst is None:
+            self.last_skipped = 0
+            return 0
+        words = torch.cat([mst["seen"], self._st["skip_count"]]).tolist()   # the one read
+        mst["seen"].zero_()
+        self._st["skip_count"].zero_()
+        self.last_skipped = int(words[1])
+        raise_on_status(1 if int(words[0]) & _lib.BGCN_STATUS_SEQUENCE else 0,
+                        index_also=" (a rootindex that does not increase strictly, a tree longer than max_pos, or a "
+                                   "label outside [0, num_classes))",
+                        suffix=f" ({self.last_skipped} updates skipped)")
+        return self.last_skipped

@@ -31,7 +31,7 @@
 //
 // Stream order is the only dependency between the launches.  No float atomics; every sum has a
 // fixed order.
-#include "bgcn_lstm.h"
+#include "bgcn_bert.h"
 
 namespace bgcn {
 namespace {
@@ -40,7 +40,7 @@ constexpr int kHeadDim = 64;
 constexpr int kQTile = BGCN_BERT_QUERY_TILE;
 constexpr int kMaxPos = 512;
 constexpr int kMaxHidden = 1024;
-constexpr int kMaxPer = kMaxHidden / kWave;   // values of one row per lane
+static_assert(kMaxHidden == kMaxPer * kWave, "ln_row holds a row in kMaxPer values per lane");
 static_assert(kQTile == 32, "one 32x32 MFMA tile of scores per key tile");
 
 // ---- setup (after k_lstm_setup).  Block 0: validity of seq_start over all sequences; one fault
@@ -75,39 +75,6 @@ __global__ __launch_bounds__(256) void k_bert_setup(SetupArgs a) {
   }
   if (a.attn_sum)
     for (int64_t i = int64_t(blockIdx.x) * 256 + t; i < a.N; i += int64_t(gridDim.x) * 256) a.attn_sum[i] = 0.f;
-}
-
-// ---- LayerNorm of one row held by one wave: lane l holds the columns l + 64 i, i < per.  Two
-// passes over the registers (mean, then the centred squares), biased variance.
-__device__ __forceinline__ void ln_row(float (&v)[kMaxPer], int per, int H, const float* __restrict__ g,
-                                       const float* __restrict__ be, float eps, int l, float* __restrict__ out,
-                                       float* rowsum) {
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < kMaxPer; ++i)
-    if (i < per) s += v[i];
-  const float mean = wave_sum(s) / float(H);
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < kMaxPer; ++i)
-    if (i < per) {
-      v[i] -= mean;
-      q = fmaf(v[i], v[i], q);
-    }
-  const float inv = 1.0f / sqrtf(wave_sum(q) / float(H) + eps);
-  float rs = 0.f;
-#pragma unroll
-  for (int i = 0; i < kMaxPer; ++i)
-    if (i < per) {
-      const int c = l + kWave * i;
-      const float y = fmaf(v[i] * inv, g[c], be[c]);
-      out[c] = y;
-      rs += y;
-    }
-  if (rowsum) {
-    rs = wave_sum(rs);
-    if (l == 0) *rowsum = rs;
-  }
 }
 
 // ---- embeddings.  Wave (b, pos): dst row = LN(x[start + pos] + pos_emb[pos] + type_emb).  Full
@@ -177,8 +144,7 @@ __global__ __launch_bounds__(256) void k_bert_add_ln(AddLnArgs a) {
   ln_row(v, per, H, a.g, a.be, a.eps, l, out, a.rowsum ? a.rowsum + r : nullptr);
 }
 
-// ---- y[r][c] = act(y[r][c] + bias[c]) in place over [M, C], C % 4 == 0; GELU: the erf form
-__device__ __forceinline__ float gelu_erf(float x) { return x * 0.5f * (1.0f + erff(x * 0.70710678118654752440f)); }
+// ---- y[r][c] = act(y[r][c] + bias[c]) in place over [M, C], C % 4 == 0; GELU: the erf form (gelu_erf)
 template <bool GELU>
 __global__ __launch_bounds__(256) void k_bert_bias_act(float* __restrict__ y, const float* __restrict__ bias,
                                                        int64_t total4, int C4) {
@@ -377,12 +343,14 @@ struct BertWs {
   int64_t* first;
 };
 
+}  // namespace
+
 bool bert_shape_ok(int64_t N, int64_t B, int64_t H, int64_t I, int64_t L) {
   return N > 0 && B > 0 && N < (int64_t(1) << 31) - 1 && B <= 65535 && H % kHeadDim == 0 && H >= 64 &&
          H <= kMaxHidden && I % 64 == 0 && I >= 64 && I <= 4096 && L >= 1 && L <= BGCN_BERT_MAX_LAYERS;
 }
 
-void carve_bert(Carve& c, int64_t N, int64_t B, int64_t H, int64_t I, bool full, BertWs* w) {
+static void carve_bert(Carve& c, int64_t N, int64_t B, int64_t H, int64_t I, bool full, BertWs* w) {
   const size_t m = size_t(full ? N : B), nb = size_t(B), h = size_t(H);
   w->h = c.take<float>(m * h);
   w->a = c.take<float>(m * h);
@@ -422,7 +390,20 @@ int bert_check_args(const bgcn_bert_args* a, const void* ws) {
   return BGCN_OK;
 }
 
-int bert_eval_impl(const bgcn_bert_args* a, void* ws, size_t ws_bytes, hipStream_t s) {
+void bert_setup(const bgcn_bert_args* a, SeqInfo sq, int64_t* first, hipStream_t s) {
+  SetupArgs su{a->seq_start, a->num_seqs, a->num_nodes, a->max_pos, sq, first, a->attn_sum, a->status};
+  hipLaunchKernelGGL(k_bert_setup, dim3(64), dim3(256), 0, s, su);
+}
+
+int bert_head(const bgcn_bert_args* a, const float* P, float* loss_row, int32_t* predw, hipStream_t s) {
+  BertHeadArgs hd{P, a->pooler_b, a->fc_w, a->fc_b, int(a->hidden), int(a->out_feats), a->y, a->logp, loss_row,
+                  predw, a->pred, a->status};
+  hipLaunchKernelGGL(k_bert_head, dim3(unsigned(a->num_seqs)), dim3(256), 0, s, hd);
+  BGCN_CHECK_LAUNCH();
+  return seq_finish(loss_row, predw, a->y, a->num_seqs, a->loss, a->correct, s);
+}
+
+static int bert_eval_impl(const bgcn_bert_args* a, void* ws, size_t ws_bytes, hipStream_t s) {
   BGCN_TRY(bert_check_args(a, ws));
   const int64_t N = a->num_nodes, B = a->num_seqs, H = a->hidden, I = a->intermediate, L = a->num_layers;
   const bool full = a->hidden_out || a->hidden_sum || a->attn_sum;
@@ -434,8 +415,7 @@ int bert_eval_impl(const bgcn_bert_args* a, void* ws, size_t ws_bytes, hipStream
   const int heads = int(a->heads);
   const unsigned rows4 = grid_for(M, 4);
 
-  SetupArgs su{a->seq_start, B, N, a->max_pos, w.sq, w.first, a->attn_sum, a->status};
-  hipLaunchKernelGGL(k_bert_setup, dim3(64), dim3(256), 0, s, su);
+  bert_setup(a, w.sq, w.first, s);
   EmbedArgs em{a->x, a->ldx, a->pos_emb, a->type_emb, a->emb_ln_w, a->emb_ln_b, w.sq, w.h, int(H), a->ln_eps, full ? 0 : 1};
   hipLaunchKernelGGL(k_bert_embed, dim3(unsigned(B), full ? grid_for(a->max_pos, 4) : 1), dim3(256), 0, s, em);
   BGCN_CHECK_LAUNCH();
@@ -480,14 +460,9 @@ int bert_eval_impl(const bgcn_bert_args* a, void* ws, size_t ws_bytes, hipStream
     roots = w.R;
   }
   BGCN_TRY(gemm_xwt_impl(roots, H, a->pooler_w, nullptr, H, H, w.P, H, B, H, H, s, nullptr));
-  BertHeadArgs hd{w.P, a->pooler_b, a->fc_w, a->fc_b, int(H), int(a->out_feats), a->y, a->logp, w.loss_row,
-                  w.predw, a->pred, a->status};
-  hipLaunchKernelGGL(k_bert_head, dim3(unsigned(B)), dim3(256), 0, s, hd);
-  BGCN_CHECK_LAUNCH();
-  return seq_finish(w.loss_row, w.predw, a->y, B, a->loss, a->correct, s);
+  return bert_head(a, w.P, w.loss_row, w.predw, s);
 }
 
-}  // namespace
 }  // namespace bgcn
 
 extern "C" size_t bgcn_bert_workspace_size(int64_t num_nodes, int64_t num_seqs, int64_t hidden, int64_t intermediate,

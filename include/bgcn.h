@@ -1348,6 +1348,86 @@ size_t bgcn_bert_workspace_size(int64_t num_nodes, int64_t num_seqs, int64_t hid
                                 int64_t num_layers, int want_full);
 int bgcn_bert_eval(const bgcn_bert_args* args, void* workspace, size_t workspace_bytes, bgcn_stream_t stream);
 
+/* --------------------------------------------------------------------------
+ * TreeBERT baseline, training: one iteration of model/Twitter/BERT_Twitter.py:89-119 up to the
+ * optimiser - BertModel in training mode (its four dropout sites), the mean NLL, the accuracy and
+ * the gradient of the loss with respect to every parameter the loss depends on (and, optionally,
+ * x) - for a whole batch of trees as one launch sequence: no host round trip, no allocation.
+ * Additive entry points: BGCN_ABI_VERSION is unchanged.
+ *
+ * Training is root-only by construction.  Position 0 attends to itself only, the pooler reads
+ * position 0 and dropout is element-wise, so the loss is a function of each sequence's first row
+ * also in training mode; the gradient of a softmax over one unmasked key is exactly 0.  `fwd` is
+ * bgcn_bert_eval's argument struct with y required and hidden_out, hidden_sum and attn_sum NULL.
+ * The forward is the root-only chain of bgcn_bert_eval on [B, hidden] (the same GEMMs, LayerNorm
+ * and head definitions) with dropout; with both rates 0 logp, loss, correct and pred are
+ * bgcn_bert_eval's bits.  The workspace keeps per layer the normalised rows and 1 / sqrt(var + eps)
+ * of both LayerNorm inputs, ctx, the attention-output LayerNorm's output, the intermediate before
+ * and after GELU, and the layer's output.
+ *
+ * Dropout.  Sites: 0 after the embeddings' LayerNorm; for layer l: 3 l + 1 on the attention
+ * probabilities, 3 l + 2 after attention.output.dense (+ bias), 3 l + 3 after output.dense
+ * (+ bias), the last two before the residual add.  Site 3 l + 1 has rate attn_dropout and one draw
+ * per (sequence b, head): the probability row of position 0 is the single value 1, so
+ * ctx[b, head] = keep v[b, head] / (1 - attn_dropout).  The others have rate hidden_dropout and one
+ * draw per (sequence b, column).  With mix32 the 32-bit mixer
+ *   x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16   (mod 2^32),
+ * a draw is
+ *   hash(seed, site, b, j) = mix32(mix32(mix32(b ^ lo32(seed)) ^ (site * 0x9E3779B9 + hi32(seed)))
+ *                                  ^ (j * 0x85EBCA6B)),      j = the column, or the head,
+ * the value is kept iff hash >= thr, thr = floor(p * 2^32 + 0.5) with the fp32 rate p taken to
+ * double, and a kept value is multiplied by the fp32 quotient 1.0f / (1.0f - p).  p = 0 keeps
+ * everything with scale exactly 1.  The backward regenerates the masks; none is stored.
+ *
+ * Backward.  dz = (softmax - onehot(y)) / B per sequence (a label outside [0, out_feats) gives a
+ * zero row and sets BGCN_STATUS_SEQUENCE); d fc_w = dz^T pooled and d fc_b = the column sums of dz
+ * over the sequences in order; through tanh and the pooler; then per layer from the last down:
+ * LayerNorm backward (one wave per row), the dropout mask, output.dense, GELU' (erf form),
+ * intermediate.dense, the second LayerNorm backward with the residual adds, attention.output.dense,
+ * the per-head mask, value; then the embeddings' LayerNorm.  Weight gradients dW = dY^T X reduce
+ * over the B rows in a fixed order, bias and LayerNorm gradients are fixed-order column sums.
+ *   - every layer's d q_w, d q_b, d k_w, d k_b are written as zeros (not skipped);
+ *   - d_pos_emb [max_pos, hidden] and d_type_emb [2, hidden] (both rows: the gradient buffer covers
+ *     the whole token_type_embeddings tensor) hold the column sums over the sequences of the
+ *     embeddings' gradient in row 0 and zeros elsewhere;
+ *   - dx [N, ldx] (optional): the hidden columns of the sequences' first rows hold their gradient,
+ *     the hidden columns of every other row zeros; columns past hidden are not written.
+ * The gradient buffers are written whole, never accumulated into.  Deterministic: no float
+ * atomics, every sum in a fixed order; two calls on the same inputs give the same bits.
+ *
+ * Validity: as bgcn_bert_eval (*status; a fault in seq_start or a length empties every sequence, a
+ * bad label adds no loss and no gradient).  *skip_flag is 1.0f when *status is non-zero after the
+ * forward, else 0.0f: the optimiser's skip flag (bgcn_adam_multi_step).  A faulted batch reads and
+ * writes nothing out of bounds and still writes every gradient buffer whole; its gradients are not
+ * to be used.
+ *
+ * BGCN_EINVAL before any HIP call: bgcn_bert_eval's conditions, a non-NULL hidden_out / hidden_sum
+ * / attn_sum, a null y / gradient pointer / skip_flag, a gradient or dx not 16-byte aligned, a
+ * dropout rate outside [0, 1), "workspace too small" (bgcn_bert_train_workspace_size; 0 for an
+ * unsupported shape).
+ * -------------------------------------------------------------------------- */
+typedef struct bgcn_bert_train_args {
+  bgcn_bert_args fwd;            /* y required; hidden_out, hidden_sum, attn_sum NULL */
+  float* d_pos_emb;              /* [max_pos, hidden]                         */
+  float* d_type_emb;             /* [2, hidden]                               */
+  float* d_emb_ln_w;             /* [hidden]                                  */
+  float* d_emb_ln_b;
+  float* d_pooler_w;             /* [hidden, hidden]                          */
+  float* d_pooler_b;
+  float* d_fc_w;                 /* [C, hidden]                               */
+  float* d_fc_b;
+  bgcn_bert_layer d_layer[BGCN_BERT_MAX_LAYERS];   /* written through: the gradients' buffers */
+  float* dx;                     /* [N, ldx] (fwd.ldx), or NULL               */
+  float* skip_flag;              /* [1]                                       */
+  uint64_t drop_seed;
+  float hidden_dropout;          /* sites 0, 3 l + 2, 3 l + 3                 */
+  float attn_dropout;            /* sites 3 l + 1                             */
+} bgcn_bert_train_args;
+size_t bgcn_bert_train_workspace_size(int64_t num_nodes, int64_t num_seqs, int64_t hidden, int64_t intermediate,
+                                      int64_t num_layers);
+int bgcn_bert_train_grad(const bgcn_bert_train_args* args, void* workspace, size_t workspace_bytes,
+                         bgcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

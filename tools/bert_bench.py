@@ -11,7 +11,17 @@ intermediate), random weights.  Timed: ``evaluate`` (the root-only form), the fu
 loop - ``transformers``' BertModel where importable, else the fp32 torch restatement of
 tests/bert_ref.py.  The root-only call is bound by the weight bytes it reads once per call; its
 achieved fraction of the HBM peak is reported against them.  Times are host clocks around work that
-ends in a device synchronise, after a warm-up.  There is no fallback: without a GPU the script fails."""
+ends in a device synchronise, after a warm-up.  There is no fallback: without a GPU the script fails.
+
+    python tools/bert_bench.py --train --out profiles/bert_train.json
+
+times one training step (``TreeBERTTrainStep.step``: root rows pooled, ``bgcn_bert_train_grad`` at
+dropout 0.1 / 0.1, the Adam launches) on the same batch, in windows of ``--window`` steps with one
+synchronise each, and ``grad_batch`` alone.  Beside the time stand the bytes a step cannot avoid
+moving at B = 24: every weight the chain reads, twice (forward, and dX = dY W in the backward), every
+dW written once, and Adam's traffic (gradient, parameter and both moments read, parameter and both
+moments written) over all tensors that get a gradient; the activations ([24, width] rows) are left
+out.  Their quotient by the HBM peak is the floor the step time is compared with."""
 import argparse
 import json
 import os
@@ -26,7 +36,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from bigcn_amd import TreeBERT                               # noqa: E402
+from bigcn_amd import TreeBERT, TreeBERTTrainStep            # noqa: E402
 from bigcn_amd.data import synth_tree_sizes                  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0   # MI355X: 8 TB/s
@@ -77,14 +87,70 @@ def reference_loop(model, encode, data, rows):
     return out, loss.item(), out.max(dim=1)[1].eq(data.y).sum().item()
 
 
+def timed_windows(fn, warmup, windows, steps):
+    """ms per call of ``fn`` over windows of ``steps`` calls that end in one device synchronise."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(windows):
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3 / steps)
+    return {"median_ms": float(np.median(ts)), "min_ms": float(np.min(ts)), "max_ms": float(np.max(ts)),
+            "windows": windows, "steps_per_window": steps}
+
+
+def train_bytes(model):
+    """The bytes one training step must move at a small B, from the shapes alone."""
+    by_name = dict(model.named_parameters())
+    names = model.names()
+    chain = [n for n in names if ".query." not in n and ".key." not in n and "position_embeddings" not in n
+             and "token_type" not in n]                      # read by the forward chain
+    gemm = [n for n in chain if by_name[n].dim() == 2]       # read again by dX = dY W
+    num = lambda ns: sum(by_name[n].numel() for n in ns)     # noqa: E731
+    parts = {"weights_read_forward": 4 * num(chain), "weights_read_backward": 4 * num(gemm),
+             "gradients_written": 4 * num(names),            # the q / k zeros and the embeddings' rows included
+             "adam_read": 4 * 4 * num(names), "adam_written": 3 * 4 * num(names)}
+    parts["total"] = sum(parts.values())
+    return parts
+
+
+def main_train(a, dev, data, model, B, N, sizes):
+    step = TreeBERTTrainStep(model, drop_seed=1)
+    rows = model._root_rows(data)
+    st = timed_windows(lambda: step.step(data), a.warmup, a.iters, a.window)
+    gb = timed_windows(lambda: model.grad_batch(rows, data.rootindex, data.y, drop_seed=1), a.warmup, a.iters, a.window)
+    skipped = step.check_status()
+    loss = float(step.step(data)[0])
+    nbytes = train_bytes(model)
+    floor_ms = nbytes["total"] / (HBM_PEAK_GBS * 1e9) * 1e3
+    res = {"device": torch.cuda.get_device_name(0), "B": B, "N": N, "tokens_per_row": a.tokens,
+           "longest_tree": int(sizes.max()), "hidden_dropout": model.hidden_dropout, "attn_dropout": model.attn_dropout,
+           "train_step": st, "grad_batch_alone": gb, "steps_taken": step.step_count, "steps_skipped": skipped,
+           "last_loss": loss, "bytes_per_step": nbytes, "hbm_peak_GBps": HBM_PEAK_GBS, "hbm_floor_ms": floor_ms,
+           "step_GBps": nbytes["total"] / (st["median_ms"] * 1e-3) / 1e9,
+           "step_time_over_hbm_floor": st["median_ms"] / floor_ms,
+           "timing": "host clock around windows of steps ending in one device synchronise, after a warm-up"}
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "bert_eval.json"))
+    ap.add_argument("--train", action="store_true", help="time the training step instead (profiles/bert_train.json)")
+    ap.add_argument("--window", type=int, default=20, help="--train: steps per timed window")
+    ap.add_argument("--out", default=None, help="default profiles/bert_eval.json, or bert_train.json with --train")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--ref-iters", type=int, default=3)
     ap.add_argument("--tokens", type=int, default=4, help="T: values pooled per row are T x 768")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join("profiles", "bert_train.json" if a.train else "bert_eval.json")
     if not torch.cuda.is_available():
         raise SystemExit("bert_bench needs a ROCm GPU (no fallback)")
     dev = torch.device("cuda:0")
@@ -97,6 +163,8 @@ def main():
                            y=torch.randint(0, 4, (B,), generator=g).to(dev))
     torch.manual_seed(seed)
     model = TreeBERT(256 * 768, 64, 64, dev, vocab=8).eval()
+    if a.train:
+        return main_train(a, dev, data, model, B, N, sizes)
     rows = model._pool(data.x.reshape(N, -1, 768))
     logp = torch.empty(B, 4, device=dev)
 
