@@ -76,6 +76,8 @@ EXPORTED_SYMBOLS = (
     "bgcn_adam_multi_table_size", "bgcn_adam_multi_plan", "bgcn_adam_multi_step", "bgcn_ebgcn_train_loss",
     "bgcn_lstm_workspace_size", "bgcn_lstm_eval", "bgcn_lstm_train_workspace_size", "bgcn_lstm_train_grad",
     "bgcn_bert_workspace_size", "bgcn_bert_eval", "bgcn_bert_train_workspace_size", "bgcn_bert_train_grad",
+    "bgcn_w16_image_size", "bgcn_w16_pack", "bgcn_gemm_xwt_w16_workspace_size", "bgcn_gemm_xwt_w16",
+    "bgcn_bert_w16_workspace_size", "bgcn_bert_eval_w16",
 )
 
 BGCN_ADAM_MULTI_MAX_TENSORS = 128
@@ -238,6 +240,16 @@ class BertArgs(Structure):
         ("pooler_w", c_void_p), ("pooler_b", c_void_p), ("fc_w", c_void_p), ("fc_b", c_void_p), ("y", c_void_p),
         ("logp", c_void_p), ("loss", c_void_p), ("correct", c_void_p), ("pred", c_void_p),
         ("hidden_out", c_void_p), ("hidden_sum", c_void_p), ("attn_sum", c_void_p), ("status", c_void_p),
+    ]
+
+
+class BertW16Args(Structure):
+    """bgcn_bert_w16_args (include/bgcn.h): ``base`` and the weight images of the root-only chain."""
+    _fields_ = [
+        ("base", BertArgs),
+        ("v_w16", c_void_p * BGCN_BERT_MAX_LAYERS), ("ao_w16", c_void_p * BGCN_BERT_MAX_LAYERS),
+        ("i_w16", c_void_p * BGCN_BERT_MAX_LAYERS), ("o_w16", c_void_p * BGCN_BERT_MAX_LAYERS),
+        ("pooler_w16", c_void_p),
     ]
 
 
@@ -427,6 +439,13 @@ _SIGS = {
     "bgcn_bert_eval": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_bert_train_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64]),
     "bgcn_bert_train_grad": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "bgcn_w16_image_size": (c_size_t, [c_int64, c_int64]),
+    "bgcn_w16_pack": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "bgcn_gemm_xwt_w16_workspace_size": (c_size_t, [c_int64, c_int64, c_int64]),
+    "bgcn_gemm_xwt_w16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                  c_void_p, c_size_t, c_void_p]),
+    "bgcn_bert_w16_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
+    "bgcn_bert_eval_w16": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

@@ -189,6 +189,74 @@ class TreeBERT(torch.nn.Module):
         st.update(key=key, args=a, held=held)
         return st
 
+    # ---- bf16 weight images of the root-only chain
+    @property
+    def weight_images(self):
+        """``"bf16"`` when the root-only calls read bf16 weight images, else ``None`` (fp32, the default)."""
+        return self.__dict__.get("_weight_images")
+
+    def use_weight_images(self, kind="bf16"):
+        """Select what the root-only calls (:meth:`evaluate`, :meth:`validate`, :meth:`forward` and a plain
+        :meth:`forward_batch`) read their GEMM weights from.  ``"bf16"``: images of the value, attention-
+        output, intermediate, output and pooler weights rounded to bf16 (nearest even), read by the split-K
+        kernel of ``bgcn_bert_eval_w16`` - half the bytes on every compute unit, and ``logp`` moves by the
+        rounding of the weights (up to about 1e-2).  ``None``: the fp32 parameters, bit for bit as before.
+
+        The images are built at the next root-only call and again whenever a source parameter was rebound,
+        moved or written (``data_ptr``, device, dtype, ``_version``), so an optimiser step or a
+        ``load_state_dict`` is picked up.  They are no parameter or buffer: ``state_dict()`` is unchanged.
+        The full form, :meth:`grad_batch` and :class:`TreeBERTTrainStep` always read the fp32 parameters.
+        Returns ``self``."""
+        if kind not in (None, "bf16"):
+            raise ValueError(f"weight images are 'bf16' or None, not {kind!r}")
+        self.__dict__["_weight_images"] = kind
+        if kind is None:
+            self.__dict__.pop("_w16", None)
+        return self
+
+    def _stale_images(self):
+        """Forget the images: a native optimiser step wrote the parameters behind torch's version counters."""
+        self.__dict__.pop("_w16", None)
+
+    def _image_sources(self):
+        """(field of bgcn_bert_w16_args, layer or None, state_dict name) of every imaged weight."""
+        out = [(f + "16", i, f"BERT.encoder.layer.{i}.{dict(_LAYER_FIELDS)[f]}")
+               for i in range(self.num_layers) for f in ("v_w", "ao_w", "i_w", "o_w")]
+        return out + [("pooler_w16", None, "BERT.pooler.dense.weight")]
+
+    def _images(self, st, dev):
+        """``bgcn_bert_w16_args`` with current images: one device buffer, repacked when a source changed."""
+        by_name = dict(self.named_parameters())
+        srcs = self._image_sources()
+        key = (dev,) + tuple((by_name[n].data_ptr(), by_name[n].device, by_name[n].dtype, by_name[n]._version)
+                             for _, _, n in srcs)
+        im = self.__dict__.get("_w16")
+        if im is not None and im["key"] == key:
+            return im["args"]
+        L = _lib.lib()
+        held = dict(zip(self.names(), st["held"]))       # fp32, contiguous, aligned, on dev (_bind)
+        sizes = [L.bgcn_w16_image_size(*held[n].shape) for _, _, n in srcs]
+        if not all(sizes):
+            raise _lib.BGCNError("bgcn_w16_pack: unsupported shape (hidden and intermediate multiples of 64 in [64, 4096])")
+        offs, total = [], 0
+        for s in sizes:
+            offs.append(total)
+            total += (s + 255) // 256 * 256
+        buf = im["buf"] if im is not None and im["buf"].numel() == total and im["buf"].device == dev \
+            else _lib.workspace(total, dev)
+        wa = _lib.BertW16Args()
+        stream = stream_handle()
+        for (field, layer, n), off in zip(srcs, offs):
+            w = held[n]
+            p = buf.data_ptr() + off
+            check(L.bgcn_w16_pack(w.data_ptr(), w.stride(0), w.size(0), w.size(1), p, stream))
+            if layer is None:
+                setattr(wa, field, p)
+            else:
+                getattr(wa, field)[layer] = p
+        self.__dict__["_w16"] = {"key": key, "buf": buf, "args": wa}
+        return wa
+
     def _pool(self, x):
         """[n, T, hidden] -> [n, hidden] over T (``BERT_Twitter.py:34-37``), one torch reduction."""
         if self.pooling == 'max':
@@ -199,9 +267,14 @@ class TreeBERT(torch.nn.Module):
 
     # ---- the native call
     def _workspace(self, st, N, B, full, dev):
-        """The form's workspace, asked for again only when ``(N, B)`` changes; never shrinks."""
+        """The form's workspace, asked for again only when ``(N, B)`` changes; never shrinks.  ``full``:
+        True, False, or ``"w16"`` (the root-only form on weight images)."""
         if st["sizes"].get(full) != (N, B):
-            need = _lib.lib().bgcn_bert_workspace_size(N, B, self.hidden, self.intermediate, self.num_layers, int(full))
+            if full == "w16":
+                need = _lib.lib().bgcn_bert_w16_workspace_size(B, self.hidden, self.intermediate, self.num_layers)
+            else:
+                need = _lib.lib().bgcn_bert_workspace_size(N, B, self.hidden, self.intermediate, self.num_layers,
+                                                           int(full))
             if need == 0:
                 raise _lib.BGCNError("bgcn_bert_eval: unsupported shape (hidden = 64 heads in [64, 1024], intermediate "
                                      "% 64 in [64, 4096], num_layers in [1, 24])")
@@ -238,7 +311,8 @@ class TreeBERT(torch.nn.Module):
                                      or hidden.numel() != N * self.hidden or hidden.device != dev):
             raise ValueError("hidden must be a contiguous fp32 [N, hidden] tensor")
         full = hidden is not None or want_sums
-        ws = self._workspace(st, N, B, full, dev)
+        w16 = not full and self.weight_images == "bf16"
+        ws = self._workspace(st, N, B, "w16" if w16 else full, dev)
         r = {"logp": logp, "hidden": hidden,
              "loss": torch.empty(1, dtype=torch.float32, device=dev) if y is not None else None,
              "correct": torch.empty(1, dtype=torch.int32, device=dev) if y is not None else None,
@@ -252,7 +326,12 @@ class TreeBERT(torch.nn.Module):
         a.hidden_out = ptr(hidden)
         a.hidden_sum = r["sums"][0].data_ptr() if want_sums else 0
         a.attn_sum = r["sums"][1].data_ptr() if want_sums else 0
-        check(_lib.lib().bgcn_bert_eval(ctypes.addressof(a), ptr(ws), ws.numel(), stream_handle()))
+        if w16:
+            wa = self._images(st, dev)
+            ctypes.memmove(ctypes.addressof(wa.base), ctypes.addressof(a), ctypes.sizeof(_lib.BertArgs))
+            check(_lib.lib().bgcn_bert_eval_w16(ctypes.addressof(wa), ptr(ws), ws.numel(), stream_handle()))
+        else:
+            check(_lib.lib().bgcn_bert_eval(ctypes.addressof(a), ptr(ws), ws.numel(), stream_handle()))
         st["seen"].bitwise_or_(st["status"])   # the call zeroes its status word; check_status reads this one
         return r
 
@@ -457,8 +536,9 @@ class ChunkedAdam:
     ``MultiAdam`` takes, as ``ceil(n / 128)`` of them over consecutive slices of the parameter list,
     one launch each.  Only the first slice is given ``skip_count``, so a skipped step counts once."""
 
-    def __init__(self, params, lr: float, weight_decay: float):
+    def __init__(self, params, lr: float, weight_decay: float, after_step=None):
         params = list(params)
+        self.after_step = after_step   # called after every step: the launches write the parameters in place
         self.chunks = [MultiAdam([{"params": params[i:i + MULTI_MAX_TENSORS]}], lr=lr, weight_decay=weight_decay)
                        for i in range(0, len(params), MULTI_MAX_TENSORS)]
 
@@ -480,6 +560,8 @@ class ChunkedAdam:
             c.step(grads=None if grads is None else grads[k:k + n], skip_flag=skip_flag,
                    skip_count=skip_count if i == 0 else None)
             k += n
+        if self.after_step is not None:
+            self.after_step()
 
     def state_dict(self) -> dict:
         """``step_count`` and, in :meth:`params` order, copies of both moments."""
@@ -504,8 +586,10 @@ class ChunkedAdam:
 def bert_adam(model, lr: float = 5e-4, weight_decay: float = 1e-4) -> ChunkedAdam:
     """The reference's optimiser (``BERT_Twitter.py``: ``Adam(model.parameters(), lr=5e-4,
     weight_decay=1e-4)``) over all of ``model.parameters()`` in their order.  ``word_embeddings`` is
-    in the list and never gets a gradient, so it is left alone, as by torch."""
-    return ChunkedAdam(model.parameters(), lr, weight_decay)
+    in the list and never gets a gradient, so it is left alone, as by torch.  Its launches write the
+    parameters behind torch's version counters, so every step also tells ``model`` to rebuild its weight
+    images (:meth:`TreeBERT.use_weight_images`) at the next root-only call."""
+    return ChunkedAdam(model.parameters(), lr, weight_decay, after_step=model._stale_images)
 
 
 class TreeBERTTrainStep:
@@ -565,6 +649,7 @@ class TreeBERTTrainStep:
         by_id = {id(by_name[n]): g for n, g in zip(m.names(), st["grads"])}
         self.optimizer.step(grads=[by_id.get(id(p)) for p in self.optimizer.params()], skip_flag=st["skip_flag"],
                             skip_count=st["skip_count"])
+        m._stale_images()
         out = (r["loss"].view(()), r["correct"].view(()))
         return out + (r["pred"],) if pred else out
 

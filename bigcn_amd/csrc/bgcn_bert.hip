@@ -31,6 +31,10 @@
 //
 // Stream order is the only dependency between the launches.  No float atomics; every sum has a
 // fixed order.
+//
+// bgcn_bert_eval_w16 is the root-only form on bf16 weight images: every GEMM a split-K product of
+// bgcn_gemm_w16.hip, its partials added by k_bert_bias_act_part / k_bert_add_ln_part (the pooler's by
+// k_w16_reduce); setup, embeddings, head and finish are the launches above.
 #include "bgcn_bert.h"
 
 namespace bgcn {
@@ -153,6 +157,76 @@ __global__ __launch_bounds__(256) void k_bert_bias_act(float* __restrict__ y, co
     float4 v = f4add(ld4(y + i * 4), ld4(bias + c));
     if constexpr (GELU) v = make_float4(gelu_erf(v.x), gelu_erf(v.y), gelu_erf(v.z), gelu_erf(v.w));
     st4(y + i * 4, v);
+  }
+}
+
+// ---- the two row kernels above for bgcn_bert_eval_w16: y is not a finished product but the S
+// partials part[s][r][c] (stride floats apart) of the split-K GEMM (bgcn_gemm_w16.hip), added here in
+// the order of s before the bias
+__device__ __forceinline__ float4 part_sum4(const float* __restrict__ part, int S, int64_t stride, int64_t i) {
+  // four loads in flight per step (one after the other, S memory latencies end to end); the order of
+  // the additions is that of s
+  float4 v = ld4(part + i);
+  int s = 1;
+  for (; s + 4 <= S; s += 4) {
+    const float4 t0 = ld4(part + s * stride + i), t1 = ld4(part + (s + 1) * stride + i);
+    const float4 t2 = ld4(part + (s + 2) * stride + i), t3 = ld4(part + (s + 3) * stride + i);
+    v = f4add(f4add(f4add(f4add(v, t0), t1), t2), t3);
+  }
+  for (; s < S; ++s) v = f4add(v, ld4(part + s * stride + i));
+  return v;
+}
+struct AddLnPartArgs {
+  const float *part, *bias, *res, *g, *be;
+  float* out;
+  int64_t M, stride;
+  int S, H;
+  float eps;
+};
+__global__ __launch_bounds__(256) void k_bert_add_ln_part(AddLnPartArgs a) {
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, H = a.H, per = H >> 6;
+  const int64_t r = int64_t(blockIdx.x) * 4 + w;
+  if (r >= a.M) return;
+  const float *y = a.part + r * H, *res = a.res + r * H;
+  float v[kMaxPer];
+#pragma unroll
+  for (int i = 0; i < kMaxPer; ++i)
+    if (i < per) v[i] = y[l + kWave * i];
+  int s = 1;
+  for (; s + 4 <= a.S; s += 4) {   // 4 per loads in flight; added in the order of s
+    float t[4][kMaxPer];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int i = 0; i < kMaxPer; ++i)
+        if (i < per) t[u][i] = y[(s + u) * a.stride + l + kWave * i];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int i = 0; i < kMaxPer; ++i)
+        if (i < per) v[i] += t[u][i];
+  }
+  for (; s < a.S; ++s)
+#pragma unroll
+    for (int i = 0; i < kMaxPer; ++i)
+      if (i < per) v[i] += y[s * a.stride + l + kWave * i];
+#pragma unroll
+  for (int i = 0; i < kMaxPer; ++i)
+    if (i < per) {
+      const int c = l + kWave * i;
+      v[i] = (v[i] + a.bias[c]) + res[c];
+    }
+  ln_row(v, per, H, a.g, a.be, a.eps, l, a.out + r * H, nullptr);
+}
+template <bool GELU>
+__global__ __launch_bounds__(256) void k_bert_bias_act_part(const float* __restrict__ part, int S, int64_t stride,
+                                                            const float* __restrict__ bias, float* __restrict__ out,
+                                                            int64_t total4, int C4) {
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < total4; i += int64_t(gridDim.x) * 256) {
+    const int c = int(i % C4) * 4;
+    float4 v = f4add(part_sum4(part, S, stride, i * 4), ld4(bias + c));
+    if constexpr (GELU) v = make_float4(gelu_erf(v.x), gelu_erf(v.y), gelu_erf(v.z), gelu_erf(v.w));
+    st4(out + i * 4, v);
   }
 }
 
@@ -463,7 +537,74 @@ static int bert_eval_impl(const bgcn_bert_args* a, void* ws, size_t ws_bytes, hi
   return bert_head(a, w.P, w.loss_row, w.predw, s);
 }
 
+// ---- the root-only form on bf16 weight images: bert_eval_impl's root-only branch with every GEMM
+// a split-K product on an image (gemm_w16_partials) whose partials the next row kernel adds
+static size_t bert_w16_part_floats(int64_t B, int64_t H, int64_t I) {
+  return std::max({w16_part_floats(B, H, H), w16_part_floats(B, I, H), w16_part_floats(B, H, I)});
+}
+
+static int bert_eval_w16_impl(const bgcn_bert_w16_args* wa, void* ws, size_t ws_bytes, hipStream_t s) {
+  BGCN_CHECK_ARG(wa, "null args");
+  const bgcn_bert_args* a = &wa->base;
+  BGCN_TRY(bert_check_args(a, ws));
+  BGCN_CHECK_ARG(!a->hidden_out && !a->hidden_sum && !a->attn_sum,
+                 "bgcn_bert_eval_w16 is the root-only form: hidden_out, hidden_sum and attn_sum must be NULL");
+  const int64_t N = a->num_nodes, B = a->num_seqs, H = a->hidden, I = a->intermediate, L = a->num_layers;
+  for (int l = 0; l < L; ++l)
+    for (const void* p : {wa->v_w16[l], wa->ao_w16[l], wa->i_w16[l], wa->o_w16[l]})
+      BGCN_CHECK_ARG(p && a16(p), "null or unaligned weight image");
+  BGCN_CHECK_ARG(wa->pooler_w16 && a16(wa->pooler_w16), "null or unaligned weight image");
+  BertWs w;
+  Carve c(ws, ws_bytes);
+  carve_bert(c, N, B, H, I, false, &w);
+  float* part = c.take<float>(bert_w16_part_floats(B, H, I));
+  BGCN_CHECK_ARG(ws && align_up(c.off, 256) <= ws_bytes, "workspace too small");   // bgcn_bert_w16_workspace_size's figure
+  const unsigned rows4 = grid_for(B, 4);
+  const int Shh = w16_splits(H, H), Sih = w16_splits(I, H), Shi = w16_splits(H, I);
+
+  bert_setup(a, w.sq, w.first, s);
+  EmbedArgs em{a->x, a->ldx, a->pos_emb, a->type_emb, a->emb_ln_w, a->emb_ln_b, w.sq, w.h, int(H), a->ln_eps, 1};
+  hipLaunchKernelGGL(k_bert_embed, dim3(unsigned(B), 1), dim3(256), 0, s, em);
+  BGCN_CHECK_LAUNCH();
+
+  const auto bias_grid = [](int64_t total4) { return dim3(unsigned(std::min<int64_t>((total4 + 255) / 256, 4096))); };
+  for (int l = 0; l < L; ++l) {
+    const bgcn_bert_layer& y = a->layer[l];
+    BGCN_TRY(gemm_w16_partials(w.h, H, wa->v_w16[l], part, B, H, H, s));   // P = 1 at position 0: ctx = v
+    hipLaunchKernelGGL(k_bert_bias_act_part<false>, bias_grid(B * H / 4), dim3(256), 0, s, part, Shh, B * H, y.v_b,
+                       w.ctx, B * H / 4, int(H / 4));
+    BGCN_TRY(gemm_w16_partials(w.ctx, H, wa->ao_w16[l], part, B, H, H, s));
+    AddLnPartArgs l1{part, y.ao_b, w.h, y.ao_ln_w, y.ao_ln_b, w.a, B, B * H, Shh, int(H), a->ln_eps};
+    hipLaunchKernelGGL(k_bert_add_ln_part, dim3(rows4), dim3(256), 0, s, l1);
+    BGCN_TRY(gemm_w16_partials(w.a, H, wa->i_w16[l], part, B, I, H, s));
+    hipLaunchKernelGGL(k_bert_bias_act_part<true>, bias_grid(B * I / 4), dim3(256), 0, s, part, Sih, B * I, y.i_b,
+                       w.inter, B * I / 4, int(I / 4));
+    BGCN_TRY(gemm_w16_partials(w.inter, I, wa->o_w16[l], part, B, H, I, s));
+    AddLnPartArgs l2{part, y.o_b, w.a, y.o_ln_w, y.o_ln_b, w.h, B, B * H, Shi, int(H), a->ln_eps};
+    hipLaunchKernelGGL(k_bert_add_ln_part, dim3(rows4), dim3(256), 0, s, l2);
+    BGCN_CHECK_LAUNCH();
+  }
+  BGCN_TRY(gemm_w16_partials(w.h, H, wa->pooler_w16, part, B, H, H, s));
+  BGCN_TRY(w16_reduce(part, Shh, B, H, nullptr, w.P, H, s));
+  return bert_head(a, w.P, w.loss_row, w.predw, s);
+}
+
 }  // namespace bgcn
+
+extern "C" size_t bgcn_bert_w16_workspace_size(int64_t num_seqs, int64_t hidden, int64_t intermediate,
+                                               int64_t num_layers) {
+  if (!bgcn::bert_shape_ok(num_seqs, num_seqs, hidden, intermediate, num_layers)) return 0;
+  bgcn::BertWs w;
+  bgcn::Carve c(nullptr, 0);
+  bgcn::carve_bert(c, num_seqs, num_seqs, hidden, intermediate, false, &w);
+  c.take<float>(bgcn::bert_w16_part_floats(num_seqs, hidden, intermediate));
+  return bgcn::align_up(c.off, 256);
+}
+
+extern "C" int bgcn_bert_eval_w16(const bgcn_bert_w16_args* args, void* workspace, size_t workspace_bytes,
+                                  bgcn_stream_t stream) {
+  return bgcn::bert_eval_w16_impl(args, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
 
 extern "C" size_t bgcn_bert_workspace_size(int64_t num_nodes, int64_t num_seqs, int64_t hidden, int64_t intermediate,
                                            int64_t num_layers, int want_full) {

@@ -199,6 +199,23 @@ __device__ __forceinline__ f32x16 mfma_x6(bf16x8 ah, bf16x8 am, bf16x8 al, bf16x
   return mfma_bf16(ah, bh, c);
 }
 
+// acc += a.b with a in PA planes and b in PB (one exact operand: three products; both split
+// three ways: six, mfma_x6)
+template <int PA, int PB>
+__device__ __forceinline__ f32x16 mfma_planes(const bf16x8 (&a)[PA], const bf16x8 (&b)[PB], f32x16 c) {
+  if constexpr (PA == 1) {
+    c = mfma_bf16(a[0], b[2], c);
+    c = mfma_bf16(a[0], b[1], c);
+    return mfma_bf16(a[0], b[0], c);
+  } else if constexpr (PB == 1) {
+    c = mfma_bf16(a[2], b[0], c);
+    c = mfma_bf16(a[1], b[0], c);
+    return mfma_bf16(a[0], b[0], c);
+  } else {
+    return mfma_x6(a[0], a[1], a[2], b[0], b[1], b[2], c);
+  }
+}
+
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 // a store of the chain's [N, 128] activations (Z1, H1, dZ2, dZ1, ...), which the next launch

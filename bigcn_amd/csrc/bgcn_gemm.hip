@@ -398,23 +398,6 @@ template <> struct XPiece<float> {
     *reinterpret_cast<bf16x8*>(planes[2] + o) = l;
   }
 };
-// acc += a.b with a in PA planes and b in PB (one exact operand: three products; both split
-// three ways: six, mfma_x6)
-template <int PA, int PB>
-__device__ __forceinline__ f32x16 mfma_planes(const bf16x8 (&a)[PA], const bf16x8 (&b)[PB], f32x16 c) {
-  if constexpr (PA == 1) {
-    c = mfma_bf16(a[0], b[2], c);
-    c = mfma_bf16(a[0], b[1], c);
-    return mfma_bf16(a[0], b[0], c);
-  } else if constexpr (PB == 1) {
-    c = mfma_bf16(a[2], b[0], c);
-    c = mfma_bf16(a[1], b[0], c);
-    return mfma_bf16(a[0], b[0], c);
-  } else {
-    return mfma_x6(a[0], a[1], a[2], b[0], b[1], b[2], c);
-  }
-}
-
 // Y[M, Nc] = X[M, K] (bf16 or fp32) . W[Nc, K]^T (fp32; rows [0, split) from W0, the rest
 // W1).  Block tile 128 x 128 (4 waves as 2 x 2, wave tile 64 x 64), K % 8 == 0, ldx % 8 == 0.
 template <class TX>

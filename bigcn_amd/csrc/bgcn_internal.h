@@ -89,6 +89,16 @@ int gemm_tn_x(const float* G, int64_t ldg, const void* X, int xdt, int64_t ldx, 
               size_t ws_bytes, hipStream_t stream, int timing_cls, const int32_t* gate);
 int tn_splits(int64_t Mc, int64_t Nc, int64_t K);
 
+// ---- skinny-M split-K GEMM on bf16 weight images (bgcn_gemm_w16.hip)
+bool w16_shape_ok(int64_t Nc, int64_t K);
+int w16_splits(int64_t Nc, int64_t K);                       // S, a function of (Nc, K) alone
+size_t w16_part_floats(int64_t M, int64_t Nc, int64_t K);    // S M Nc
+// part[s][m][n], s < S: the partial products of X[M, K] (fp32, 16-byte aligned rows) . W16[Nc, K]^T
+int gemm_w16_partials(const float* X, int64_t ldx, const void* image, float* part, int64_t M, int64_t Nc, int64_t K,
+                      hipStream_t s);
+// Y[m][n] = the partials added in the order of s, then bias[n] (or nullptr)
+int w16_reduce(const float* part, int S, int64_t M, int64_t Nc, const float* bias, float* Y, int64_t ldy, hipStream_t s);
+
 // ---- classifier head fc -> log_softmax -> NLL (BiGCN_Twitter.py:129-130,186) and its
 // row-local backward; evaluated per tree by one wave (shared by k_readout_fwd's fused
 // form and bgcn_step.hip)

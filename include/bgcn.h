@@ -1428,6 +1428,61 @@ size_t bgcn_bert_train_workspace_size(int64_t num_nodes, int64_t num_seqs, int64
 int bgcn_bert_train_grad(const bgcn_bert_train_args* args, void* workspace, size_t workspace_bytes,
                          bgcn_stream_t stream);
 
+/* --------------------------------------------------------------------------
+ * bf16 weight images and the skinny-M split-K GEMM that reads them; the TreeBERT root-only
+ * evaluation on them.  Additive entry points: BGCN_ABI_VERSION is unchanged.
+ *
+ * The root-only chain of bgcn_bert_eval is [B, hidden] GEMMs whose cost is reading each weight
+ * once; a 128-column block tile gives such a product 6 - 24 workgroups.  Here the weights are kept
+ * as bf16 images (half the bytes) and K is split over waves and workgroups, so that a 768 x 768
+ * product already is 288 workgroups.  Opt-in: the rounding of the weights moves logp by up to
+ * 1.5e-2 on the project's test cases, and a split sum has other fp32 bits than bgcn_gemm_xwt's.
+ *
+ * Image.  bgcn_w16_pack rounds W [Nc, K] (fp32, row stride ldw >= K) to bf16, to nearest even -
+ * the bits of torch's .to(torch.bfloat16) - and stores it tiled in the operand order of
+ * v_mfma_f32_32x32x16_bf16 (32 columns x 16 k = 1 KB per tile, the k-tiles of a column tile
+ * consecutive).  The layout is the library's; bgcn_w16_image_size gives the bytes (0 for an
+ * unsupported shape: Nc and K multiples of 64 in [64, 4096]).  image: 16-byte aligned.
+ *
+ * bgcn_gemm_xwt_w16: Y[M, Nc] = X[M, K] . W16[Nc, K]^T (+ bias[Nc]) for any M >= 1.  The bf16
+ * weight is an exact MFMA operand, the fp32 activation is split into three bf16 planes, three
+ * products per k-step, fp32 accumulate: given the rounded weights the product is fp32-grade.  The
+ * four waves of a workgroup take different k-slices of one 32-column tile and add their
+ * accumulators through LDS in wave order; each workgroup writes one partial into the workspace and
+ * a second launch adds the partials in order, then the bias.  The split is a function of (Nc, K)
+ * alone, so a row's bits do not depend on the other rows of the call.  No float atomics: two calls
+ * give the same bits.  Nothing but Y's M x Nc elements and the workspace is written.  X and Y: 16-
+ * byte aligned rows (ldx % 4, ldy % 4); bias: 16-byte aligned or NULL.
+ *
+ * bgcn_bert_eval_w16: bgcn_bert_eval's root-only form with the value, attention-output,
+ * intermediate and output products of every layer and the pooler's read from images (packed from
+ * v_w, ao_w, i_w, o_w and pooler_w); the partials are added by the row kernel that follows.  The
+ * embeddings, biases, LayerNorm parameters and fc stay fp32 and come from `base`, which is checked
+ * as bgcn_bert_eval checks it and must have hidden_out, hidden_sum and attn_sum NULL; the q and k
+ * weights are never read.  Validity (*status) is bgcn_bert_eval's.
+ *
+ * BGCN_EINVAL before any HIP call: bgcn_bert_eval's conditions, a non-NULL hidden_out / hidden_sum
+ * / attn_sum, "null or unaligned weight image", "workspace too small"
+ * (bgcn_bert_w16_workspace_size; 0 for an unsupported shape).
+ * -------------------------------------------------------------------------- */
+size_t bgcn_w16_image_size(int64_t Nc, int64_t K);
+int bgcn_w16_pack(const float* W, int64_t ldw, int64_t Nc, int64_t K, void* image, bgcn_stream_t stream);
+size_t bgcn_gemm_xwt_w16_workspace_size(int64_t M, int64_t Nc, int64_t K);
+int bgcn_gemm_xwt_w16(const float* X, int64_t ldx, const void* image, const float* bias, float* Y, int64_t ldy,
+                      int64_t M, int64_t Nc, int64_t K, void* workspace, size_t workspace_bytes,
+                      bgcn_stream_t stream);
+typedef struct bgcn_bert_w16_args {
+  bgcn_bert_args base;           /* hidden_out, hidden_sum, attn_sum NULL     */
+  const void* v_w16[BGCN_BERT_MAX_LAYERS];    /* images of layer[l].v_w  [hidden, hidden]        */
+  const void* ao_w16[BGCN_BERT_MAX_LAYERS];   /*           layer[l].ao_w [hidden, hidden]        */
+  const void* i_w16[BGCN_BERT_MAX_LAYERS];    /*           layer[l].i_w  [intermediate, hidden]  */
+  const void* o_w16[BGCN_BERT_MAX_LAYERS];    /*           layer[l].o_w  [hidden, intermediate]  */
+  const void* pooler_w16;                     /*           pooler_w      [hidden, hidden]        */
+} bgcn_bert_w16_args;
+size_t bgcn_bert_w16_workspace_size(int64_t num_seqs, int64_t hidden, int64_t intermediate, int64_t num_layers);
+int bgcn_bert_eval_w16(const bgcn_bert_w16_args* args, void* workspace, size_t workspace_bytes,
+                       bgcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

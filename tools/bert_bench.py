@@ -13,6 +13,13 @@ tests/bert_ref.py.  The root-only call is bound by the weight bytes it reads onc
 achieved fraction of the HBM peak is reported against them.  Times are host clocks around work that
 ends in a device synchronise, after a warm-up.  There is no fallback: without a GPU the script fails.
 
+    python tools/bert_bench.py --weights both
+
+times ``evaluate`` on the fp32 parameters and on bf16 weight images (``TreeBERT.use_weight_images("bf16")``:
+half the weight bytes, read by the split-K kernel of ``bgcn_bert_eval_w16``) in one process on the same
+batch, and writes profiles/bert_eval_w16.json: medians, min / max, the weight bytes a call reads and their
+share of the 8 TB/s HBM peak per leg.
+
     python tools/bert_bench.py --train --out profiles/bert_train.json
 
 times one training step (``TreeBERTTrainStep.step``: root rows pooled, ``bgcn_bert_train_grad`` at
@@ -139,8 +146,41 @@ def main_train(a, dev, data, model, B, N, sizes):
     print(json.dumps(res))
 
 
+def main_weights(a, dev, data, model, B, N, sizes):
+    """``--weights bf16 / both``: ``evaluate`` on the fp32 parameters and on the bf16 weight images, in one
+    process on the same batch; per leg the weight bytes one call reads and their share of the HBM peak."""
+    by_name = dict(model.named_parameters())
+    read = [n for n in model.names() if ".query." not in n and ".key." not in n
+            and "position_embeddings" not in n and "token_type" not in n]
+    imaged = {n for _, _, n in model._image_sources()}
+    nbytes = {"fp32": 4 * sum(by_name[n].numel() for n in read),
+              "bf16": sum((2 if n in imaged else 4) * by_name[n].numel() for n in read)}
+    res = {"device": torch.cuda.get_device_name(0), "B": B, "N": N, "tokens_per_row": a.tokens,
+           "longest_tree": int(sizes.max()), "hbm_peak_GBps": HBM_PEAK_GBS,
+           "timing": "host clock around one evaluate() and a device synchronise, after a warm-up; both legs in one "
+                     "process on the same batch"}
+    logp = {}
+    for leg in (("fp32", "bf16") if a.weights == "both" else (a.weights,)):
+        model.use_weight_images(None if leg == "fp32" else "bf16")
+        logp[leg] = torch.empty(B, 4, device=dev)
+        t = timed(lambda: model.evaluate(data, logp=logp[leg]), a.warmup, a.iters)
+        model.check_status()
+        gbs = nbytes[leg] / (t["median_ms"] * 1e-3) / 1e9
+        res["evaluate_" + leg] = dict(t, weight_bytes_per_call=nbytes[leg], GBps=gbs,
+                                      fraction_of_hbm_peak=gbs / HBM_PEAK_GBS)
+    if a.weights == "both":
+        res["ratio_fp32_over_bf16"] = res["evaluate_fp32"]["median_ms"] / res["evaluate_bf16"]["median_ms"]
+        res["max_abs_logp_diff_bf16_vs_fp32"] = float((logp["bf16"] - logp["fp32"]).abs().max())
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--weights", choices=("fp32", "bf16", "both"), default="fp32",
+                    help="what evaluate() reads its GEMM weights from; bf16 / both time TreeBERT.use_weight_images "
+                         "and write profiles/bert_eval_w16.json")
     ap.add_argument("--train", action="store_true", help="time the training step instead (profiles/bert_train.json)")
     ap.add_argument("--window", type=int, default=20, help="--train: steps per timed window")
     ap.add_argument("--out", default=None, help="default profiles/bert_eval.json, or bert_train.json with --train")
@@ -150,7 +190,8 @@ def main():
     ap.add_argument("--tokens", type=int, default=4, help="T: values pooled per row are T x 768")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join("profiles", "bert_train.json" if a.train else "bert_eval.json")
+        a.out = os.path.join("profiles", "bert_train.json" if a.train else
+                             "bert_eval.json" if a.weights == "fp32" else "bert_eval_w16.json")
     if not torch.cuda.is_available():
         raise SystemExit("bert_bench needs a ROCm GPU (no fallback)")
     dev = torch.device("cuda:0")
@@ -165,6 +206,8 @@ def main():
     model = TreeBERT(256 * 768, 64, 64, dev, vocab=8).eval()
     if a.train:
         return main_train(a, dev, data, model, B, N, sizes)
+    if a.weights != "fp32":
+        return main_weights(a, dev, data, model, B, N, sizes)
     rows = model._pool(data.x.reshape(N, -1, 768))
     logp = torch.empty(B, 4, device=dev)
 
