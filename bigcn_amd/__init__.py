@@ -37,7 +37,9 @@ Drop-in symbols for the reference's hot path (cwkd/BiGCN):
 * ``TreeBERTTrainStep`` / ``bert_adam`` - the BERT baseline's training-loop body (BERT_Twitter.py:89-119):
   the forward with ``BertModel``'s four dropout sites, the loss and the backward on the trees' root rows
   as one native call (``bgcn_bert_train_grad``, also ``TreeBERT.grad_batch``), then the reference's Adam
-  as ``MultiAdam`` launches over slices of 128 tensors
+  as ``MultiAdam`` launches over slices of 128 tensors; ``gemm="skinny"`` runs the chain's products on the
+  split fp32 kernels (``bgcn_bert_train_grad_skinny``; alone: ``ops.gemm_xwt_skinny`` / ``gemm_xw_skinny`` /
+  ``gemm_tn_skinny``), which put a ``[B, hidden]`` product on 256 or more workgroups
 * ``FusedTrainStep`` - the training-loop body (BiGCN_Twitter.py:183-189) as one native call
   + the data-parallel all-reduce + fused Adam
 

@@ -78,6 +78,8 @@ EXPORTED_SYMBOLS = (
     "bgcn_bert_workspace_size", "bgcn_bert_eval", "bgcn_bert_train_workspace_size", "bgcn_bert_train_grad",
     "bgcn_w16_image_size", "bgcn_w16_pack", "bgcn_gemm_xwt_w16_workspace_size", "bgcn_gemm_xwt_w16",
     "bgcn_bert_w16_workspace_size", "bgcn_bert_eval_w16",
+    "bgcn_gemm_skinny_workspace_size", "bgcn_gemm_xwt_skinny", "bgcn_gemm_xw_skinny", "bgcn_gemm_tn_skinny",
+    "bgcn_bert_train_skinny_workspace_size", "bgcn_bert_train_grad_skinny",
 )
 
 BGCN_ADAM_MULTI_MAX_TENSORS = 128
@@ -446,6 +448,15 @@ _SIGS = {
                                   c_void_p, c_size_t, c_void_p]),
     "bgcn_bert_w16_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
     "bgcn_bert_eval_w16": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "bgcn_gemm_skinny_workspace_size": (c_size_t, [c_int64, c_int64, c_int64]),
+    "bgcn_gemm_xwt_skinny": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                     c_int64, c_void_p, c_size_t, c_void_p]),
+    "bgcn_gemm_xw_skinny": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                    c_void_p, c_size_t, c_void_p]),
+    "bgcn_gemm_tn_skinny": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                    c_void_p]),
+    "bgcn_bert_train_skinny_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64]),
+    "bgcn_bert_train_grad_skinny": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),

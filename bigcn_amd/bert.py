@@ -52,6 +52,9 @@ _TOP_FIELDS = (("pos_emb", "BERT.embeddings.position_embeddings.weight"),
                ("pooler_w", "BERT.pooler.dense.weight"), ("pooler_b", "BERT.pooler.dense.bias"),
                ("fc_w", "fc.weight"), ("fc_b", "fc.bias"))
 LN_EPS = 1e-12   # BertConfig.layer_norm_eps
+# grad_batch's ``gemm``: the workspace's key in TreeBERT._state, its size function, the native call
+_TRAIN_GEMMS = {"tiled": ("train", "bgcn_bert_train_workspace_size", "bgcn_bert_train_grad"),
+                "skinny": ("train_skinny", "bgcn_bert_train_skinny_workspace_size", "bgcn_bert_train_grad_skinny")}
 
 
 def _holder(**children):
@@ -336,9 +339,12 @@ class TreeBERT(torch.nn.Module):
         return r
 
     def _train(self, x, rootindex, y, dx=False, grads=None, want_pred=False, skip_flag=None, drop_seed=0,
-               hidden_dropout=None, attn_dropout=None):
-        """One ``bgcn_bert_train_grad`` call.  ``grads``: fp32 contiguous buffers in :meth:`names` order
-        (default: new ones)."""
+               hidden_dropout=None, attn_dropout=None, gemm="tiled"):
+        """One ``bgcn_bert_train_grad`` call (``gemm="skinny"``: ``bgcn_bert_train_grad_skinny``).  ``grads``:
+        fp32 contiguous buffers in :meth:`names` order (default: new ones)."""
+        if gemm not in _TRAIN_GEMMS:
+            raise ValueError(f"gemm must be 'tiled' or 'skinny', not {gemm!r}")
+        form, size_fn, grad_fn = _TRAIN_GEMMS[gemm]
         if not x.is_cuda:
             raise _lib.BGCNError("bigcn_amd ops take device tensors (no CPU path)")
         if x.dim() != 2 or x.size(1) != self.hidden:
@@ -355,15 +361,15 @@ class TreeBERT(torch.nn.Module):
         y = y.to(device=dev, dtype=torch.int64).contiguous()
         if y.numel() != B:
             raise ValueError("y must have one label per tree")
-        if st["sizes"].get("train") != B:
-            need = _lib.lib().bgcn_bert_train_workspace_size(N, B, self.hidden, self.intermediate, self.num_layers)
+        if st["sizes"].get(form) != B:
+            need = getattr(_lib.lib(), size_fn)(N, B, self.hidden, self.intermediate, self.num_layers)
             if need == 0:
-                raise _lib.BGCNError("bgcn_bert_train_grad: unsupported shape (hidden = 64 heads in [64, 1024], "
+                raise _lib.BGCNError(f"{grad_fn}: unsupported shape (hidden = 64 heads in [64, 1024], "
                                      "intermediate % 64 in [64, 4096], num_layers in [1, 24])")
-            if st["ws"].get("train") is None or st["ws"]["train"].numel() < need or st["ws"]["train"].device != dev:
-                st["ws"]["train"] = _lib.workspace(need, dev)
-            st["sizes"]["train"] = B
-        ws = st["ws"]["train"]
+            if st["ws"].get(form) is None or st["ws"][form].numel() < need or st["ws"][form].device != dev:
+                st["ws"][form] = _lib.workspace(need, dev)
+            st["sizes"][form] = B
+        ws = st["ws"][form]
         r = {"logp": torch.empty(B, C, dtype=torch.float32, device=dev),
              "loss": torch.empty(1, dtype=torch.float32, device=dev),
              "correct": torch.empty(1, dtype=torch.int32, device=dev),
@@ -393,12 +399,13 @@ class TreeBERT(torch.nn.Module):
         ta.dx, ta.skip_flag, ta.drop_seed = ptr(gx), skip_flag.data_ptr(), int(drop_seed) & (2 ** 64 - 1)
         ta.hidden_dropout = self.hidden_dropout if hidden_dropout is None else float(hidden_dropout)
         ta.attn_dropout = self.attn_dropout if attn_dropout is None else float(attn_dropout)
-        check(_lib.lib().bgcn_bert_train_grad(ctypes.addressof(ta), ptr(ws), ws.numel(), stream_handle()))
+        check(getattr(_lib.lib(), grad_fn)(ctypes.addressof(ta), ptr(ws), ws.numel(), stream_handle()))
         st["seen"].bitwise_or_(st["status"])
         r.update(grads=grads, dx=None if gx is None else gx[:, :self.hidden], skip_flag=skip_flag)
         return r
 
-    def grad_batch(self, x, rootindex, y, dx=False, drop_seed=0, hidden_dropout=None, attn_dropout=None):
+    def grad_batch(self, x, rootindex, y, dx=False, drop_seed=0, hidden_dropout=None, attn_dropout=None,
+                   gemm="tiled"):
         """Forward in training mode, mean NLL loss and backward of one batch of trees
         (``BERT_Twitter.py:89-119`` up to ``optimizer.step()``) as one native call: ``(loss, correct,
         grads)``, 0-dim fp32 / int32 device tensors and a dict of the loss's gradients keyed by the
@@ -407,9 +414,15 @@ class TreeBERT(torch.nn.Module):
         hidden]``: the root rows' gradient, zeros elsewhere) with ``dx=True``.  Only the trees' first
         rows of ``x`` are read.  The dropout masks are a function of ``drop_seed``; the rates default
         to the module's.  New tensors on every call; ``.grad`` is not touched; no host sync.  Validity:
-        :meth:`check_status`; the gradients of a flagged batch are not to be used."""
+        :meth:`check_status`; the gradients of a flagged batch are not to be used.
+
+        ``gemm`` selects the kernels of the chain's products: ``"tiled"`` (the default) the block-tiled
+        GEMMs, whose forward has :meth:`evaluate`'s bits; ``"skinny"`` the split kernels of
+        ``bgcn_bert_train_grad_skinny``, which put each ``[B, hidden]`` product on 256 or more workgroups
+        and read the fp32 parameters as they are.  Same masks, same contract; the results agree within
+        fp32 rounding, not bit for bit.  Any other string raises ``ValueError``."""
         r = self._train(x, rootindex, y, dx=dx, drop_seed=drop_seed, hidden_dropout=hidden_dropout,
-                        attn_dropout=attn_dropout)
+                        attn_dropout=attn_dropout, gemm=gemm)
         grads = dict(zip(self.names(), r["grads"]))
         if dx:
             grads["x"] = r["dx"]
@@ -599,9 +612,14 @@ class TreeBERTTrainStep:
     its masks from ``drop_seed + k`` (``drop_seed=None``: drawn once from torch's generator); the seed
     of the last step is ``last_drop_seed``.  An invalid batch is decided on the device: the call sets
     the optimiser's ``skip_flag``, the update writes nothing, and :meth:`check_status` reports it with
-    one read.  ``.grad`` is left alone."""
+    one read.  ``.grad`` is left alone.  ``gemm``: as :meth:`TreeBERT.grad_batch` takes it (``"tiled"``, the
+    default, or ``"skinny"``)."""
 
-    def __init__(self, model: TreeBERT, optimizer=None, lr: float = 5e-4, weight_decay: float = 1e-4, drop_seed=None):
+    def __init__(self, model: TreeBERT, optimizer=None, lr: float = 5e-4, weight_decay: float = 1e-4, drop_seed=None,
+                 gemm="tiled"):
+        if gemm not in _TRAIN_GEMMS:
+            raise ValueError(f"gemm must be 'tiled' or 'skinny', not {gemm!r}")
+        self.gemm = gemm
         self.model = model
         self.optimizer = bert_adam(model, lr, weight_decay) if optimizer is None else optimizer
         self.drop_seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if drop_seed is None else int(drop_seed)
@@ -644,7 +662,7 @@ class TreeBERTTrainStep:
         self.last_drop_seed = (self.drop_seed + self._steps) & (2 ** 64 - 1)
         self._steps += 1
         r = m._train(m._root_rows(data), data.rootindex, data.y, grads=st["grads"], want_pred=pred,
-                     skip_flag=st["skip_flag"], drop_seed=self.last_drop_seed)
+                     skip_flag=st["skip_flag"], drop_seed=self.last_drop_seed, gemm=self.gemm)
         by_name = dict(m.named_parameters())
         by_id = {id(by_name[n]): g for n, g in zip(m.names(), st["grads"])}
         self.optimizer.step(grads=[by_id.get(id(p)) for p in self.optimizer.params()], skip_flag=st["skip_flag"],

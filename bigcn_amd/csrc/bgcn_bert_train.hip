@@ -14,7 +14,7 @@
 //   3l + 3 after output.dense (rate hidden_dropout, j = column).  Masks are regenerated in the
 //   backward, never stored.
 //
-//   forward   bert_setup (k_bert_setup); k_bt_embed; per layer gemm_xwt_impl as bgcn_bert_eval's
+//   forward   bert_setup (k_bert_setup); k_bt_embed; per layer the products of bgcn_bert_eval's
 //             root-only chain with k_bt_ctx (v + bias, the head's draw), k_bt_add_ln (dropout,
 //             residual, LN; keeps the normalised row and 1 / sqrt(var + eps)), k_bt_inter (bias, the
 //             pre-GELU value kept, GELU); bert_head (k_bert_head, seq_finish)
@@ -24,8 +24,12 @@
 //             attention.output.dense, k_bt_head_mask, value; k_bt_zero for q / k;
 //             the embeddings' k_bt_ln_bwd, the column sums into row 0 of d position / d type,
 //             k_bt_zero for their other rows, k_bt_dx_zero + k_bt_dx_roots
-//   dW = dY^T X through gemm_tn_impl (reduction over the B rows, also B = 1), dX = dY W through
-//   gemm_xw2_impl.
+//   dW = dY^T X (reduction over the B rows, also B = 1), dX = dY W.
+//
+// The three products (Y = X W^T, dX = dY W, dW = dY^T X) are a policy the two entry points instantiate:
+// TiledGemms (gemm_xwt_impl, gemm_xw2_impl, gemm_tn_impl: bgcn_bert_train_grad, whose forward has
+// bgcn_bert_eval's bits) and SkinnyGemms (bgcn_gemm_skinny.hip: bgcn_bert_train_grad_skinny).  The row
+// kernels and the launch order are one text.
 //
 // Stream order is the only dependency between the launches.  No float atomics; every sum has a
 // fixed order.
@@ -349,14 +353,54 @@ struct BertTrainWs {
   float *t, *P, *pooled, *dz, *dP;   // [B, H] x 3, [B, 64], [B, H]
   float *gA, *gB, *gX, *dy, *term, *dbr, *lin;   // [B, H] backward rows
   float* dI;                                      // [B, I]
-  void* tn;
-  size_t tn_bytes;
+  void* gemm;                                     // the products' own workspace (the policy's)
+  size_t gemm_bytes;
   SeqInfo sq;
   float* loss_row;
   int32_t* predw;
   int64_t* first;
 };
 
+// ---- the chain's three products, as the two entry points run them (all operands contiguous):
+//   xwt  Y[M, Nc] = X[M, K] . W[Nc, K]^T     xw  Y[M, K] = G[M, Nc] . W[Nc, K]     tn  dW[Nc, K] = G[M, Nc]^T . X[M, K]
+// ws_bytes: what they need of the call's workspace for the weights [H, H], [I, H] and [H, I].
+struct TiledGemms {   // bgcn_gemm.hip's block-tiled kernels: bgcn_bert_train_grad
+  void* ws;
+  size_t bytes;
+  hipStream_t s;
+  static size_t ws_bytes(int64_t B, int64_t H, int64_t I) {
+    return std::max(std::max(tn_ws_size(H, I, B), tn_ws_size(I, H, B)), tn_ws_size(H, H, B));
+  }
+  int xwt(const float* X, const float* W, float* Y, int64_t M, int64_t Nc, int64_t K) const {
+    return gemm_xwt_impl(X, K, W, nullptr, K, Nc, Y, Nc, M, Nc, K, s, nullptr);
+  }
+  int xw(const float* G, const float* W, float* Y, int64_t M, int64_t Nc, int64_t K) const {
+    return gemm_xw2_impl(G, Nc, W, nullptr, K, Nc, Y, K, M, K, Nc, s);
+  }
+  int tn(const float* G, const float* X, float* dW, int64_t M, int64_t Nc, int64_t K) const {
+    return gemm_tn_impl(G, Nc, X, K, dW, nullptr, K, Nc, Nc, K, M, ws, bytes, s, -1, nullptr);
+  }
+};
+struct SkinnyGemms {   // bgcn_gemm_skinny.hip's split kernels: bgcn_bert_train_grad_skinny
+  void* ws;
+  size_t bytes;
+  hipStream_t s;
+  static size_t ws_bytes(int64_t B, int64_t H, int64_t I) {
+    return sizeof(float) * std::max(std::max(skinny_part_floats(B, H, I), skinny_part_floats(B, I, H)),
+                                    skinny_part_floats(B, H, H));
+  }
+  int xwt(const float* X, const float* W, float* Y, int64_t M, int64_t Nc, int64_t K) const {
+    return gemm_xwt_skinny_impl(X, K, W, K, nullptr, Y, Nc, M, Nc, K, static_cast<float*>(ws), s);
+  }
+  int xw(const float* G, const float* W, float* Y, int64_t M, int64_t Nc, int64_t K) const {
+    return gemm_xw_skinny_impl(G, Nc, W, K, Y, K, M, Nc, K, static_cast<float*>(ws), s);
+  }
+  int tn(const float* G, const float* X, float* dW, int64_t M, int64_t Nc, int64_t K) const {
+    return gemm_tn_skinny_impl(G, Nc, X, K, dW, K, M, Nc, K, s);
+  }
+};
+
+template <class Gemms>
 size_t carve_bert_train(Carve& c, int64_t B, int64_t H, int64_t I, int64_t L, BertTrainWs* w) {
   const size_t nb = size_t(B), bh = nb * size_t(H), bi = nb * size_t(I);
   for (int l = 0; l <= L; ++l) w->hs[l] = c.take<float>(bh);
@@ -376,8 +420,8 @@ size_t carve_bert_train(Carve& c, int64_t B, int64_t H, int64_t I, int64_t L, Be
   for (float** p : rows) *p = c.take<float>(bh);
   w->dz = c.take<float>(nb * kMaxOut);
   w->dI = c.take<float>(bi);
-  w->tn_bytes = std::max(std::max(tn_ws_size(H, I, B), tn_ws_size(I, H, B)), tn_ws_size(H, H, B));
-  w->tn = c.take<char>(w->tn_bytes);
+  w->gemm_bytes = Gemms::ws_bytes(B, H, I);
+  w->gemm = c.take<char>(w->gemm_bytes);
   w->sq.start = c.take<int32_t>(nb);
   w->sq.len = c.take<int32_t>(nb);
   w->loss_row = c.take<float>(nb);
@@ -389,6 +433,7 @@ size_t carve_bert_train(Carve& c, int64_t B, int64_t H, int64_t I, int64_t L, Be
 bool rate_ok(float p) { return p >= 0.f && p < 1.f; }   // false for a NaN
 uint32_t drop_threshold(float p) { return uint32_t(std::floor(double(p) * 4294967296.0 + 0.5)); }
 
+template <class Gemms>
 int bert_train_grad_impl(const bgcn_bert_train_args* ta, void* ws, size_t ws_bytes, hipStream_t s) {
   BGCN_CHECK_ARG(ta, "null args");
   const bgcn_bert_args* a = &ta->fwd;
@@ -411,8 +456,9 @@ int bert_train_grad_impl(const bgcn_bert_train_args* ta, void* ws, size_t ws_byt
   }
   BertTrainWs w;
   Carve c(ws, ws_bytes);
-  carve_bert_train(c, B, H, I, L, &w);
-  BGCN_CHECK_ARG(ws && align_up(c.off, 256) <= ws_bytes, "workspace too small");   // bgcn_bert_train_workspace_size's figure
+  carve_bert_train<Gemms>(c, B, H, I, L, &w);
+  BGCN_CHECK_ARG(ws && align_up(c.off, 256) <= ws_bytes, "workspace too small");   // the entry's own size function's figure
+  const Gemms mm{w.gemm, w.gemm_bytes, s};
 
   Drop d{ta->drop_seed, drop_threshold(ta->hidden_dropout), drop_threshold(ta->attn_dropout),
          1.0f / (1.0f - ta->hidden_dropout), 1.0f / (1.0f - ta->attn_dropout)};
@@ -430,26 +476,26 @@ int bert_train_grad_impl(const bgcn_bert_train_args* ta, void* ws, size_t ws_byt
   for (int l = 0; l < L; ++l) {
     const bgcn_bert_layer& y = a->layer[l];
     const uint32_t site = 3u * uint32_t(l);
-    BGCN_TRY(gemm_xwt_impl(w.hs[l], H, y.v_w, nullptr, H, H, w.ctx[l], H, B, H, H, s, nullptr));
+    BGCN_TRY(mm.xwt(w.hs[l], y.v_w, w.ctx[l], B, H, H));
     hipLaunchKernelGGL(k_bt_ctx, ew_grid(B * H / 4), dim3(256), 0, s, w.ctx[l], y.v_b, B * H / 4, int(H / 4), d,
                        site + 1);
     BGCN_CHECK_LAUNCH();
-    BGCN_TRY(gemm_xwt_impl(w.ctx[l], H, y.ao_w, nullptr, H, H, w.t, H, B, H, H, s, nullptr));
+    BGCN_TRY(mm.xwt(w.ctx[l], y.ao_w, w.t, B, H, H));
     AddLnTArgs l1{w.t, y.ao_b, w.hs[l], y.ao_ln_w, y.ao_ln_b, w.a[l], w.xh1[l], w.inv1[l], B, iH, a->ln_eps, d, site + 2};
     hipLaunchKernelGGL(k_bt_add_ln, dim3(rows4), dim3(256), 0, s, l1);
-    BGCN_TRY(gemm_xwt_impl(w.a[l], H, y.i_w, nullptr, H, I, w.m[l], I, B, I, H, s, nullptr));
+    BGCN_TRY(mm.xwt(w.a[l], y.i_w, w.m[l], B, I, H));
     hipLaunchKernelGGL(k_bt_inter, ew_grid(B * I / 4), dim3(256), 0, s, w.m[l], y.i_b, w.g[l], B * I / 4, int(I / 4));
-    BGCN_TRY(gemm_xwt_impl(w.g[l], I, y.o_w, nullptr, I, H, w.t, H, B, H, I, s, nullptr));
+    BGCN_TRY(mm.xwt(w.g[l], y.o_w, w.t, B, H, I));
     AddLnTArgs l2{w.t, y.o_b, w.a[l], y.o_ln_w, y.o_ln_b, w.hs[l + 1], w.xh2[l], w.inv2[l], B, iH, a->ln_eps, d, site + 3};
     hipLaunchKernelGGL(k_bt_add_ln, dim3(rows4), dim3(256), 0, s, l2);
     BGCN_CHECK_LAUNCH();
   }
-  BGCN_TRY(gemm_xwt_impl(w.hs[L], H, a->pooler_w, nullptr, H, H, w.P, H, B, H, H, s, nullptr));
+  BGCN_TRY(mm.xwt(w.hs[L], a->pooler_w, w.P, B, H, H));
   BGCN_TRY(bert_head(a, w.P, w.loss_row, w.predw, s));
 
   // ---- backward: the head and the pooler
-  const auto tn = [&](const float* G, int64_t Mc, const float* X, int64_t Nc, float* dW) {
-    return gemm_tn_impl(G, Mc, X, Nc, dW, nullptr, Nc, Mc, Mc, Nc, B, w.tn, w.tn_bytes, s, -1, nullptr);
+  const auto tn = [&](const float* G, int64_t Nc, const float* X, int64_t K, float* dW) {
+    return mm.tn(G, X, dW, B, Nc, K);
   };
   const auto colsum = [&](int jobs, int Cc, const float* A0, float* o0, const float* A1 = nullptr, float* o1 = nullptr,
                           const float* A2 = nullptr, float* o2 = nullptr, const float* A3 = nullptr, float* o3 = nullptr) {
@@ -463,7 +509,7 @@ int bert_train_grad_impl(const bgcn_bert_train_args* ta, void* ws, size_t ws_byt
   colsum(1, iH, w.dP, ta->d_pooler_b);
   BGCN_CHECK_LAUNCH();
   BGCN_TRY(tn(w.dP, H, w.hs[L], H, ta->d_pooler_w));
-  BGCN_TRY(gemm_xw2_impl(w.dP, H, a->pooler_w, nullptr, H, H, w.gA, H, B, H, H, s));
+  BGCN_TRY(mm.xw(w.dP, a->pooler_w, w.gA, B, H, H));
 
   // ---- backward through the layers: the layer output's gradient is gA (+ gB below the last layer)
   const float* gB = nullptr;
@@ -475,18 +521,18 @@ int bert_train_grad_impl(const bgcn_bert_train_args* ta, void* ws, size_t ws_byt
     colsum(3, iH, w.term, grad(dl.o_ln_w), w.dy, grad(dl.o_ln_b), w.dbr, grad(dl.o_b));
     BGCN_CHECK_LAUNCH();
     BGCN_TRY(tn(w.dbr, H, w.g[l], I, grad(dl.o_w)));
-    BGCN_TRY(gemm_xw2_impl(w.dbr, H, y.o_w, nullptr, I, H, w.dI, I, B, I, H, s));
+    BGCN_TRY(mm.xw(w.dbr, y.o_w, w.dI, B, H, I));
     hipLaunchKernelGGL(k_bt_gelu_bwd, ew_grid(B * I / 4), dim3(256), 0, s, w.dI, w.m[l], B * I / 4);
     colsum(1, iI, w.dI, grad(dl.i_b));
     BGCN_CHECK_LAUNCH();
     BGCN_TRY(tn(w.dI, I, w.a[l], H, grad(dl.i_w)));
-    BGCN_TRY(gemm_xw2_impl(w.dI, I, y.i_w, nullptr, H, I, w.lin, H, B, H, I, s));
+    BGCN_TRY(mm.xw(w.dI, y.i_w, w.lin, B, I, H));
     LnBwdArgs b1{w.gX, w.lin, w.xh1[l], w.inv1[l], y.ao_ln_w, w.dy, w.term, w.gA, w.dbr, B, iH, d, -1, site + 2};
     hipLaunchKernelGGL(k_bt_ln_bwd, dim3(rows4), dim3(256), 0, s, b1);
     colsum(3, iH, w.term, grad(dl.ao_ln_w), w.dy, grad(dl.ao_ln_b), w.dbr, grad(dl.ao_b));
     BGCN_CHECK_LAUNCH();
     BGCN_TRY(tn(w.dbr, H, w.ctx[l], H, grad(dl.ao_w)));
-    BGCN_TRY(gemm_xw2_impl(w.dbr, H, y.ao_w, nullptr, H, H, w.lin, H, B, H, H, s));
+    BGCN_TRY(mm.xw(w.dbr, y.ao_w, w.lin, B, H, H));
     hipLaunchKernelGGL(k_bt_head_mask, ew_grid(B * H / 4), dim3(256), 0, s, w.lin, B * H / 4, int(H / 4), d,
                        uint32_t(site + 1));
     colsum(1, iH, w.lin, grad(dl.v_b));
@@ -495,7 +541,7 @@ int bert_train_grad_impl(const bgcn_bert_train_args* ta, void* ws, size_t ws_byt
                        zq);
     BGCN_CHECK_LAUNCH();
     BGCN_TRY(tn(w.lin, H, w.hs[l], H, grad(dl.v_w)));
-    BGCN_TRY(gemm_xw2_impl(w.lin, H, y.v_w, nullptr, H, H, w.gB, H, B, H, H, s));
+    BGCN_TRY(mm.xw(w.lin, y.v_w, w.gB, B, H, H));
     gB = w.gB;
   }
 
@@ -522,10 +568,25 @@ extern "C" size_t bgcn_bert_train_workspace_size(int64_t num_nodes, int64_t num_
   if (!bgcn::bert_shape_ok(num_nodes, num_seqs, hidden, intermediate, num_layers)) return 0;
   bgcn::BertTrainWs w;
   bgcn::Carve c(nullptr, 0);
-  return bgcn::carve_bert_train(c, num_seqs, hidden, intermediate, num_layers, &w);
+  return bgcn::carve_bert_train<bgcn::TiledGemms>(c, num_seqs, hidden, intermediate, num_layers, &w);
 }
 
 extern "C" int bgcn_bert_train_grad(const bgcn_bert_train_args* args, void* workspace, size_t workspace_bytes,
                                     bgcn_stream_t stream) {
-  return bgcn::bert_train_grad_impl(args, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+  return bgcn::bert_train_grad_impl<bgcn::TiledGemms>(args, workspace, workspace_bytes,
+                                                      reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t bgcn_bert_train_skinny_workspace_size(int64_t num_nodes, int64_t num_seqs, int64_t hidden,
+                                                        int64_t intermediate, int64_t num_layers) {
+  if (!bgcn::bert_shape_ok(num_nodes, num_seqs, hidden, intermediate, num_layers)) return 0;
+  bgcn::BertTrainWs w;
+  bgcn::Carve c(nullptr, 0);
+  return bgcn::carve_bert_train<bgcn::SkinnyGemms>(c, num_seqs, hidden, intermediate, num_layers, &w);
+}
+
+extern "C" int bgcn_bert_train_grad_skinny(const bgcn_bert_train_args* args, void* workspace, size_t workspace_bytes,
+                                           bgcn_stream_t stream) {
+  return bgcn::bert_train_grad_impl<bgcn::SkinnyGemms>(args, workspace, workspace_bytes,
+                                                       reinterpret_cast<hipStream_t>(stream));
 }

@@ -99,6 +99,18 @@ int gemm_w16_partials(const float* X, int64_t ldx, const void* image, float* par
 // Y[m][n] = the partials added in the order of s, then bias[n] (or nullptr)
 int w16_reduce(const float* part, int S, int64_t M, int64_t Nc, const float* bias, float* Y, int64_t ldy, hipStream_t s);
 
+// ---- skinny-M GEMMs on fp32 weights (bgcn_gemm_skinny.hip); shapes as w16_shape_ok, 16-byte aligned rows
+int skinny_splits_xwt(int64_t Nc, int64_t K);   // S of X W^T and of G W for a weight W[Nc, K]: functions of
+int skinny_splits_xw(int64_t Nc, int64_t K);    // (Nc, K) alone
+size_t skinny_part_floats(int64_t M, int64_t Nc, int64_t K);   // the partials of either product of W[Nc, K]
+// Y[M, Nc] = X[M, K] . W[Nc, K]^T (+ bias), Y[M, K] = G[M, Nc] . W[Nc, K], dW[Nc, K] = G[M, Nc]^T . X[M, K]
+int gemm_xwt_skinny_impl(const float* X, int64_t ldx, const float* W, int64_t ldw, const float* bias, float* Y,
+                         int64_t ldy, int64_t M, int64_t Nc, int64_t K, float* part, hipStream_t s);
+int gemm_xw_skinny_impl(const float* G, int64_t ldg, const float* W, int64_t ldw, float* Y, int64_t ldy, int64_t M,
+                        int64_t Nc, int64_t K, float* part, hipStream_t s);
+int gemm_tn_skinny_impl(const float* G, int64_t ldg, const float* X, int64_t ldx, float* dW, int64_t ldw, int64_t M,
+                        int64_t Nc, int64_t K, hipStream_t s);
+
 // ---- classifier head fc -> log_softmax -> NLL (BiGCN_Twitter.py:129-130,186) and its
 // row-local backward; evaluated per tree by one wave (shared by k_readout_fwd's fused
 // form and bgcn_step.hip)

@@ -323,6 +323,75 @@ def _linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def _rows_ok(t: torch.Tensor) -> bool:
+    """A 2-D fp32 tensor the skinny kernels read in place: unit column stride, 16-byte aligned rows."""
+    return (t.dim() == 2 and t.dtype == torch.float32 and t.stride(1) == 1 and t.stride(0) % 4 == 0
+            and t.stride(0) >= t.size(1) and t.data_ptr() % 16 == 0)
+
+
+def _skinny_operands(what, a, b, out, out_shape):
+    _dev_check(a, b, out)
+    if a.dim() != 2 or b.dim() != 2:
+        raise ValueError(f"{what}: the operands must be 2-D")
+    a, b = (t if _rows_ok(t) else t.float().contiguous() for t in (a, b))
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.float32, device=a.device)
+    elif tuple(out.shape) != tuple(out_shape) or not _rows_ok(out) or out.device != a.device:
+        raise ValueError(f"{what}: out must be an fp32 {tuple(out_shape)} device tensor with 16-byte aligned rows")
+    return a, b, out
+
+
+def _skinny_workspace(what, M, Nc, K, dev):
+    need = _lib.lib().bgcn_gemm_skinny_workspace_size(M, Nc, K)
+    if need == 0:
+        raise _lib.BGCNError(f"{what}: unsupported shape (M >= 1, Nc and K multiples of 64 in [64, 4096])")
+    return workspace(need, dev)
+
+
+def gemm_xwt_skinny(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``x [M, K] . w [Nc, K]^T (+ bias [Nc])`` for a few rows against a large fp32 weight read as it is
+    stored (``bgcn_gemm_xwt_skinny``: K split over 256 or more workgroups, the partials added in a fixed
+    order; a row's bits do not depend on ``M``).  ``Nc``, ``K``: multiples of 64 in [64, 4096].  No autograd."""
+    if x.dim() == 2 and w.dim() == 2 and x.size(1) != w.size(1):
+        raise ValueError("gemm_xwt_skinny: x [M, K] and w [Nc, K] must share K")
+    x, w, out = _skinny_operands("gemm_xwt_skinny", x, w, out, (x.size(0), w.size(0)))
+    _dev_check(bias)
+    if bias is not None:
+        if bias.numel() != w.size(0):
+            raise ValueError("gemm_xwt_skinny: bias must have Nc elements")
+        bias = bias.float().contiguous()
+    M, K, Nc = x.size(0), x.size(1), w.size(0)
+    ws = _skinny_workspace("gemm_xwt_skinny", M, Nc, K, x.device)
+    check(_lib.lib().bgcn_gemm_xwt_skinny(ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(out), out.stride(0),
+                                          M, Nc, K, ptr(ws), ws.numel(), stream_handle()))
+    return out
+
+
+def gemm_xw_skinny(g: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``g [M, Nc] . w [Nc, K]``, the input gradient of :func:`gemm_xwt_skinny` (``bgcn_gemm_xw_skinny``: the rows
+    of ``w`` split over the workgroups).  No autograd."""
+    if g.dim() == 2 and w.dim() == 2 and g.size(1) != w.size(0):
+        raise ValueError("gemm_xw_skinny: g [M, Nc] and w [Nc, K] must share Nc")
+    g, w, out = _skinny_operands("gemm_xw_skinny", g, w, out, (g.size(0), w.size(1)))
+    M, Nc, K = g.size(0), w.size(0), w.size(1)
+    ws = _skinny_workspace("gemm_xw_skinny", M, Nc, K, g.device)
+    check(_lib.lib().bgcn_gemm_xw_skinny(ptr(g), g.stride(0), ptr(w), w.stride(0), ptr(out), out.stride(0), M, Nc, K,
+                                         ptr(ws), ws.numel(), stream_handle()))
+    return out
+
+
+def gemm_tn_skinny(g: torch.Tensor, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``g [M, Nc]^T . x [M, K]``, the weight gradient of :func:`gemm_xwt_skinny` (``bgcn_gemm_tn_skinny``: one wave
+    per 32 x 64 tile of the result, the ``M`` rows in ascending order).  No autograd."""
+    if g.dim() == 2 and x.dim() == 2 and g.size(0) != x.size(0):
+        raise ValueError("gemm_tn_skinny: g [M, Nc] and x [M, K] must share M")
+    g, x, out = _skinny_operands("gemm_tn_skinny", g, x, out, (g.size(1), x.size(1)))
+    check(_lib.lib().bgcn_gemm_tn_skinny(ptr(g), g.stride(0), ptr(x), x.stride(0), ptr(out), out.stride(0), g.size(0),
+                                         g.size(1), x.size(1), stream_handle()))
+    return out
+
+
 def _aggregate(g: Graph, z: torch.Tensor, bias, O: int) -> torch.Tensor:
     """``A_hat z + b`` for z of padded width; the first O columns, contiguous."""
     b = None if bias is None else _pad4(bias.view(1, -1)).view(-1)

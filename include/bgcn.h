@@ -1483,6 +1483,55 @@ size_t bgcn_bert_w16_workspace_size(int64_t num_seqs, int64_t hidden, int64_t in
 int bgcn_bert_eval_w16(const bgcn_bert_w16_args* args, void* workspace, size_t workspace_bytes,
                        bgcn_stream_t stream);
 
+/* --------------------------------------------------------------------------
+ * Skinny-M split GEMMs on fp32 weights, and TreeBERT's training call on them.  Additive entry
+ * points: BGCN_ABI_VERSION is unchanged.
+ *
+ * The chain of bgcn_bert_train_grad is [B, hidden] GEMMs against weights that the optimiser
+ * rewrites at every step, so an image of them (above) is stale at once.  These three products read
+ * the weight W [Nc, K] row-major as the parameter tensor stores it (row stride ldw), fp32 in and
+ * out, and split the work until a 768 x 768 weight is 288 workgroups:
+ *   bgcn_gemm_xwt_skinny   Y[M, Nc] = X[M, K] . W^T (+ bias[Nc]);  K is split into S slices
+ *   bgcn_gemm_xw_skinny    Y[M, K]  = G[M, Nc] . W;                the rows of W are split into S
+ *   bgcn_gemm_tn_skinny    dW[Nc, K] = G[M, Nc]^T . X[M, K];       one wave per 32 x 64 tile of dW,
+ *                          the M rows in ascending order, no split and no workspace
+ * The first two write S partials [S][M][width] into the workspace; a second launch adds them in
+ * slice order, then the bias.  S is a function of (Nc, K) alone (the largest slice that leaves at
+ * least 256 workgroups), never of M: row r of Y has the same bits whatever other rows the call
+ * holds.  Arithmetic: v_mfma_f32_32x32x2_f32, fp32 operands and accumulator (an fmaf chain per
+ * element): nothing is rounded but the sums, integer operands give exact results.  No float atomics:
+ * two calls give the same bits.  Nothing but the output's elements and the workspace is written.
+ *
+ * Shapes: M >= 1, Nc and K multiples of 64 in [64, 4096].  Every matrix: non-null, 16-byte aligned,
+ * row stride a multiple of 4 and at least the row width; bias 16-byte aligned or NULL.  workspace:
+ * 16-byte aligned, bgcn_gemm_skinny_workspace_size(M, Nc, K) bytes (one figure for both split
+ * products of a weight [Nc, K]; 0 for an unsupported shape).
+ *
+ * bgcn_bert_train_grad_skinny: bgcn_bert_train_grad with its products (value, attention.output,
+ * intermediate, output and the pooler, forward and both backward products of each) on the kernels
+ * above.  Same argument struct, same contract - validity, *skip_flag, *status, the dropout hash and
+ * sites, exact-zero q / k gradients, every buffer written whole, deterministic - with one
+ * exception: a split sum has other fp32 bits than bgcn_gemm_xwt's, so the forward is within fp32
+ * rounding of bgcn_bert_eval's, not bit for bit.  The workspace is its own
+ * (bgcn_bert_train_skinny_workspace_size; 0 for an unsupported shape).
+ *
+ * BGCN_EINVAL before any HIP call: an unsupported shape, a null or unaligned pointer, ld % 4 != 0,
+ * ld below the row width, "workspace too small"; for the training call bgcn_bert_train_grad's
+ * conditions.
+ * -------------------------------------------------------------------------- */
+size_t bgcn_gemm_skinny_workspace_size(int64_t M, int64_t Nc, int64_t K);
+int bgcn_gemm_xwt_skinny(const float* X, int64_t ldx, const float* W, int64_t ldw, const float* bias, float* Y,
+                         int64_t ldy, int64_t M, int64_t Nc, int64_t K, void* workspace, size_t workspace_bytes,
+                         bgcn_stream_t stream);
+int bgcn_gemm_xw_skinny(const float* G, int64_t ldg, const float* W, int64_t ldw, float* Y, int64_t ldy, int64_t M,
+                        int64_t Nc, int64_t K, void* workspace, size_t workspace_bytes, bgcn_stream_t stream);
+int bgcn_gemm_tn_skinny(const float* G, int64_t ldg, const float* X, int64_t ldx, float* dW, int64_t ldw, int64_t M,
+                        int64_t Nc, int64_t K, bgcn_stream_t stream);
+size_t bgcn_bert_train_skinny_workspace_size(int64_t num_nodes, int64_t num_seqs, int64_t hidden,
+                                             int64_t intermediate, int64_t num_layers);
+int bgcn_bert_train_grad_skinny(const bgcn_bert_train_args* args, void* workspace, size_t workspace_bytes,
+                                bgcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

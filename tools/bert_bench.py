@@ -28,7 +28,15 @@ synchronise each, and ``grad_batch`` alone.  Beside the time stand the bytes a s
 moving at B = 24: every weight the chain reads, twice (forward, and dX = dY W in the backward), every
 dW written once, and Adam's traffic (gradient, parameter and both moments read, parameter and both
 moments written) over all tensors that get a gradient; the activations ([24, width] rows) are left
-out.  Their quotient by the HBM peak is the floor the step time is compared with."""
+out.  Their quotient by the HBM peak is the floor the step time is compared with.
+
+    python tools/bert_bench.py --train --gemm both
+
+times the same step and ``grad_batch`` on both GEMM paths (``gemm="tiled"``, the default path, and
+``gemm="skinny"``, the split fp32 kernels of ``bgcn_bert_train_grad_skinny``) in one process on twin models
+and the same batch, the windows of the two legs interleaved, and writes profiles/bert_train_skinny.json:
+per leg the median and min / max, the bytes of ``train_bytes`` and the achieved GB/s.  The skinny leg counts
+as a gain only when its median lies below the tiled leg's minimum."""
 import argparse
 import json
 import os
@@ -110,6 +118,24 @@ def timed_windows(fn, warmup, windows, steps):
             "windows": windows, "steps_per_window": steps}
 
 
+def timed_windows_interleaved(fns, warmup, windows, steps):
+    """``timed_windows`` for several callables at once: window k of every one before window k + 1 of any."""
+    for fn in fns.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    ts = {k: [] for k in fns}
+    for _ in range(windows):
+        for k, fn in fns.items():
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                fn()
+            torch.cuda.synchronize()
+            ts[k].append((time.perf_counter() - t0) * 1e3 / steps)
+    return {k: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v)), "max_ms": float(np.max(v)),
+                "windows": windows, "steps_per_window": steps} for k, v in ts.items()}
+
+
 def train_bytes(model):
     """The bytes one training step must move at a small B, from the shapes alone."""
     by_name = dict(model.named_parameters())
@@ -141,6 +167,38 @@ def main_train(a, dev, data, model, B, N, sizes):
            "step_GBps": nbytes["total"] / (st["median_ms"] * 1e-3) / 1e9,
            "step_time_over_hbm_floor": st["median_ms"] / floor_ms,
            "timing": "host clock around windows of steps ending in one device synchronise, after a warm-up"}
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+def main_train_gemms(a, dev, data, model, B, N, sizes):
+    """``--train --gemm both``: the step and ``grad_batch`` on both GEMM paths, interleaved, on twin models."""
+    legs = ("tiled", "skinny")
+    twin = TreeBERT(256 * 768, 64, 64, dev, vocab=8).eval()
+    twin.load_state_dict(model.state_dict())
+    models = dict(zip(legs, (model, twin)))
+    steps = {k: TreeBERTTrainStep(models[k], drop_seed=1, gemm=k) for k in legs}
+    rows = model._root_rows(data)
+    st = timed_windows_interleaved({k: (lambda k=k: steps[k].step(data)) for k in legs}, a.warmup, a.iters, a.window)
+    gb = timed_windows_interleaved(
+        {k: (lambda k=k: models[k].grad_batch(rows, data.rootindex, data.y, drop_seed=1, gemm=k)) for k in legs},
+        a.warmup, a.iters, a.window)
+    nbytes = train_bytes(model)
+    res = {"device": torch.cuda.get_device_name(0), "B": B, "N": N, "tokens_per_row": a.tokens,
+           "longest_tree": int(sizes.max()), "hidden_dropout": model.hidden_dropout, "attn_dropout": model.attn_dropout,
+           "bytes_per_step": nbytes, "hbm_peak_GBps": HBM_PEAK_GBS,
+           "hbm_floor_ms": nbytes["total"] / (HBM_PEAK_GBS * 1e9) * 1e3,
+           "timing": "host clock around windows of steps ending in one device synchronise, after a warm-up; window k "
+                     "of both legs before window k + 1 of either, one process, twin models, the same batch"}
+    for k in legs:
+        res[k] = {"train_step": dict(st[k], GBps=nbytes["total"] / (st[k]["median_ms"] * 1e-3) / 1e9),
+                  "grad_batch_alone": gb[k], "steps_taken": steps[k].step_count, "steps_skipped": steps[k].check_status(),
+                  "last_loss": float(steps[k].step(data)[0])}
+    for what in ("train_step", "grad_batch_alone"):
+        t, k = res["tiled"][what], res["skinny"][what]
+        res[what + "_comparison"] = {"tiled_median_over_skinny_median": t["median_ms"] / k["median_ms"],
+                                     "skinny_median_below_tiled_min": k["median_ms"] < t["min_ms"]}
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res))
@@ -183,6 +241,8 @@ def main():
                          "and write profiles/bert_eval_w16.json")
     ap.add_argument("--train", action="store_true", help="time the training step instead (profiles/bert_train.json)")
     ap.add_argument("--window", type=int, default=20, help="--train: steps per timed window")
+    ap.add_argument("--gemm", choices=("tiled", "both"), default="tiled",
+                    help="--train: both times gemm='tiled' and gemm='skinny' interleaved (profiles/bert_train_skinny.json)")
     ap.add_argument("--out", default=None, help="default profiles/bert_eval.json, or bert_train.json with --train")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
@@ -190,7 +250,8 @@ def main():
     ap.add_argument("--tokens", type=int, default=4, help="T: values pooled per row are T x 768")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join("profiles", "bert_train.json" if a.train else
+        a.out = os.path.join("profiles", "bert_train_skinny.json" if a.train and a.gemm == "both" else
+                             "bert_train.json" if a.train else
                              "bert_eval.json" if a.weights == "fp32" else "bert_eval_w16.json")
     if not torch.cuda.is_available():
         raise SystemExit("bert_bench needs a ROCm GPU (no fallback)")
@@ -205,7 +266,7 @@ def main():
     torch.manual_seed(seed)
     model = TreeBERT(256 * 768, 64, 64, dev, vocab=8).eval()
     if a.train:
-        return main_train(a, dev, data, model, B, N, sizes)
+        return (main_train_gemms if a.gemm == "both" else main_train)(a, dev, data, model, B, N, sizes)
     if a.weights != "fp32":
         return main_weights(a, dev, data, model, B, N, sizes)
     rows = model._pool(data.x.reshape(N, -1, 768))
