@@ -40,6 +40,10 @@ Drop-in symbols for the reference's hot path (cwkd/BiGCN):
   as ``MultiAdam`` launches over slices of 128 tensors; ``gemm="skinny"`` runs the chain's products on the
   split fp32 kernels (``bgcn_bert_train_grad_skinny``; alone: ``ops.gemm_xwt_skinny`` / ``gemm_xw_skinny`` /
   ``gemm_tn_skinny``), which put a ``[B, hidden]`` product on 256 or more workgroups
+* ``TweetEncoder`` - the step that makes ``data.x`` and ``data.cls`` (Process/getPHEMEgraph.py:104-118): a
+  plain bidirectional ``BertModel`` over token ids as one native call per tree of tweets
+  (``bgcn_bert_encode``: embeddings gathered by token id, unmasked MFMA attention with its K / V tiles
+  staged in LDS, a last layer that runs on the ``[n, hidden]`` first rows only)
 * ``FusedTrainStep`` - the training-loop body (BiGCN_Twitter.py:183-189) as one native call
   + the data-parallel all-reduce + fused Adam
 
@@ -51,7 +55,7 @@ from .compare import compare, rank_similarity, tree_centrality
 from .ebgcn import EBGCN
 from .explain import explain, segment_rank
 from .lstm import LSTM, LSTMTrainStep, lstm_adam
-from .bert import TreeBERT, TreeBERTTrainStep, bert_adam
+from .bert import TreeBERT, TreeBERTTrainStep, TweetEncoder, bert_adam
 from . import metrics
 from .metrics import EpochMetrics, class_metrics, confusion, evaluation4class, evaluationclass
 from .ops import (Graph, bigcn_encoder, build_graph, ebgcn_conv2_lin_train, edge_infer, edge_infer_train,
@@ -68,5 +72,6 @@ __all__ = ["GCNConv", "scatter_mean", "TDrumorGCN", "BUrumorGCN", "BiGCN", "Net"
            "explain", "segment_rank",
            "compare", "tree_centrality", "rank_similarity",
            "LSTM", "LSTMTrainStep", "lstm_adam", "TreeBERT", "TreeBERTTrainStep", "bert_adam",
+           "TweetEncoder",
            "metrics", "confusion", "class_metrics", "evaluation4class", "evaluationclass", "EpochMetrics"]
 __version__ = "0.1.0"

@@ -46,6 +46,7 @@ BGCN_LSTM_SEQ_TILE = 32   # sequences per workgroup of a step launch of bgcn_lst
 BGCN_LSTM_MAX_LAYERS = 4
 BGCN_BERT_MAX_LAYERS = 24
 BGCN_BERT_QUERY_TILE = 32   # queries per workgroup of bgcn_bert_eval's attention kernel
+BGCN_STATUS_TOKEN = 512   # bgcn_bert_encode: a token id outside [0, vocab)
 
 # every symbol include/bgcn.h declares (checked by tests/test_capi.py)
 EXPORTED_SYMBOLS = (
@@ -80,6 +81,7 @@ EXPORTED_SYMBOLS = (
     "bgcn_bert_w16_workspace_size", "bgcn_bert_eval_w16",
     "bgcn_gemm_skinny_workspace_size", "bgcn_gemm_xwt_skinny", "bgcn_gemm_xw_skinny", "bgcn_gemm_tn_skinny",
     "bgcn_bert_train_skinny_workspace_size", "bgcn_bert_train_grad_skinny",
+    "bgcn_bert_encode_workspace_size", "bgcn_bert_encode",
 )
 
 BGCN_ADAM_MULTI_MAX_TENSORS = 128
@@ -242,6 +244,21 @@ class BertArgs(Structure):
         ("pooler_w", c_void_p), ("pooler_b", c_void_p), ("fc_w", c_void_p), ("fc_b", c_void_p), ("y", c_void_p),
         ("logp", c_void_p), ("loss", c_void_p), ("correct", c_void_p), ("pred", c_void_p),
         ("hidden_out", c_void_p), ("hidden_sum", c_void_p), ("attn_sum", c_void_p), ("status", c_void_p),
+    ]
+
+
+class BertEncodeArgs(Structure):
+    """bgcn_bert_encode_args (include/bgcn.h)."""
+    _fields_ = [
+        ("input_ids", c_void_p), ("num_seqs", c_int64), ("seq_len", c_int64), ("vocab", c_int64),
+        ("hidden", c_int64), ("heads", c_int64), ("intermediate", c_int64), ("num_layers", c_int64),
+        ("max_pos", c_int64), ("ln_eps", c_float), ("reserved", c_int32),
+        ("word_emb", c_void_p), ("pos_emb", c_void_p), ("type_emb", c_void_p), ("emb_ln_w", c_void_p),
+        ("emb_ln_b", c_void_p),
+        ("layer", BertLayer * BGCN_BERT_MAX_LAYERS),
+        ("pooler_w", c_void_p), ("pooler_b", c_void_p), ("embeddings", c_void_p), ("ld_embeddings", c_int64),
+        ("cls", c_void_p), ("hidden_out", c_void_p), ("status", c_void_p),
+        ("last_layer_full", c_int32), ("embed_only", c_int32),
     ]
 
 
@@ -457,6 +474,8 @@ _SIGS = {
                                     c_void_p]),
     "bgcn_bert_train_skinny_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64]),
     "bgcn_bert_train_grad_skinny": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "bgcn_bert_encode_workspace_size": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int]),
+    "bgcn_bert_encode": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "bgcn_set_kernel_timing": (c_int, [c_int]),
     "bgcn_kernel_timing": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
     "bgcn_kernel_span": (c_int, [c_int, POINTER(c_float), POINTER(c_int64)]),
@@ -513,10 +532,13 @@ def check(rc: int) -> None:
 def raise_on_status(word: int, bits: int = 1 | 2 | 8, index_also: str = "", suffix: str = "") -> None:
     """Raise what a status word of the library reports, looking at ``bits`` only: 8 an internal
     hand-off timed out, 1 an index out of range (``index_also`` names what else sets it in the
-    caller's kernels), 2 a label out of range.  ``suffix`` ends either ``IndexError``'s message."""
+    caller's kernels), 2 a label out of range, ``BGCN_STATUS_TOKEN`` a token id outside the vocabulary.
+    ``suffix`` ends every ``IndexError``'s message."""
     word &= bits
     if word & 8:
         raise RuntimeError("libbgcn: an internal cross-workgroup hand-off timed out")
+    if word & BGCN_STATUS_TOKEN:
+        raise IndexError("input_ids holds a token id outside [0, vocab)" + suffix)
     if word & 1:
         raise IndexError("the batch holds an edge, root or tree index out of range" + index_also + suffix)
     if word & 2:

@@ -26,6 +26,9 @@ in row 0 only, ``word_embeddings`` none.  :class:`TreeBERTTrainStep` adds the re
 (:func:`bert_adam`: BERT-base's 200 tensors as consecutive :class:`MultiAdam` slices) with no host
 sync.  The per-tree ``forward`` stays an evaluation call and raises in training mode: there is no
 autograd path through it.
+
+:class:`TweetEncoder` is the step that makes ``data.x`` and ``data.cls`` (``Process/getPHEMEgraph.py:104-118``):
+a plain bidirectional ``BertModel`` over token ids, one native call (``bgcn_bert_encode``) per tree of tweets.
 """
 from __future__ import annotations
 
@@ -80,6 +83,74 @@ def _bert_holders(hidden, intermediate, num_layers, max_pos, vocab):
                            token_type_embeddings=Emb(2, hidden), LayerNorm=LN(hidden, eps=LN_EPS)),
         encoder=_holder(layer=torch.nn.ModuleList([layer() for _ in range(num_layers)])),
         pooler=_holder(dense=Lin(hidden, hidden)))
+
+
+def _bert_init(holders):
+    """BERT's initialisation: Linear and embedding weights normal with std 0.02, biases 0."""
+    with torch.no_grad():
+        for m in holders.modules():
+            if isinstance(m, (torch.nn.Linear, torch.nn.Embedding)):
+                m.weight.normal_(mean=0.0, std=0.02)
+                if getattr(m, "bias", None) is not None:
+                    m.bias.zero_()
+
+
+def _bind_weights(owner, names, top_fields, dev, new_args):
+    """``owner._state`` with the argument struct ``new_args()`` holding the parameters ``names`` (the
+    ``top_fields``, then every layer's ``_LAYER_FIELDS``), refilled only when a parameter was rebound, moved
+    or (a tensor the kernels cannot read in place: not fp32 / contiguous / 16-byte aligned / on ``dev``)
+    changed.  The state also holds the call's status word, the word :func:`_take_seen` reads and the
+    workspaces (:func:`_grow_workspace`).  Shared by :class:`TreeBERT` and :class:`TweetEncoder`."""
+    by_name = dict(owner.named_parameters())
+    src = [by_name[n] for n in names]
+    direct = [t.dtype == torch.float32 and t.is_contiguous() and t.device == dev and t.data_ptr() % 16 == 0
+              for t in src]
+    key = (dev,) + tuple((t.data_ptr(), t.dtype, None if ok else t._version) for t, ok in zip(src, direct))
+    st = owner.__dict__.get("_state")
+    if st is not None and st["key"] == key:
+        return st
+    held = [t.detach() if ok else t.detach().to(device=dev, dtype=torch.float32).contiguous().clone()
+            for t, ok in zip(src, direct)]
+    a = new_args()
+    it = iter(held)
+    for field, _ in top_fields:
+        setattr(a, field, next(it).data_ptr())
+    for i in range(owner.num_layers):
+        for field, _ in _LAYER_FIELDS:
+            setattr(a.layer[i], field, next(it).data_ptr())
+    a.hidden, a.heads, a.intermediate, a.num_layers = owner.hidden, owner.heads, owner.intermediate, owner.num_layers
+    a.max_pos, a.ln_eps = owner.max_pos, LN_EPS
+    if st is None or st["status"].device != dev:
+        st = {"status": torch.zeros(1, dtype=torch.int32, device=dev),
+              "seen": torch.zeros(1, dtype=torch.int32, device=dev), "sizes": {}, "ws": {}}
+        owner.__dict__["_state"] = st
+    a.status = st["status"].data_ptr()
+    st.update(key=key, args=a, held=held)
+    return st
+
+
+def _grow_workspace(st, form, shape, need, what, dev):
+    """``st``'s workspace of one form of a call, asked for again (``need()`` bytes) only when ``shape``
+    changes; never shrinks."""
+    if st["sizes"].get(form) != shape:
+        n = need()
+        if n == 0:
+            raise _lib.BGCNError(f"{what}: unsupported shape (hidden = 64 heads in [64, 1024], intermediate "
+                                 "% 64 in [64, 4096], num_layers in [1, 24])")
+        if st["ws"].get(form) is None or st["ws"][form].numel() < n or st["ws"][form].device != dev:
+            st["ws"][form] = _lib.workspace(n, dev)
+        st["sizes"][form] = shape
+    return st["ws"][form]
+
+
+def _take_seen(owner) -> int:
+    """One host sync: the status bits of ``owner``'s calls since the last read, which it clears."""
+    st = owner.__dict__.get("_state")
+    if st is None:
+        return 0
+    s = int(st["seen"].item())
+    st["seen"].zero_()
+    return s
 
 
 @dataclass
@@ -137,12 +208,7 @@ class TreeBERT(torch.nn.Module):
         self.hidden_dropout, self.attn_dropout = float(hidden_dropout), float(attn_dropout)
         self.BERT = _bert_holders(hidden, intermediate, num_layers, max_pos, vocab)
         self.fc = torch.nn.Linear(hidden, num_classes)
-        with torch.no_grad():
-            for m in self.BERT.modules():
-                if isinstance(m, (torch.nn.Linear, torch.nn.Embedding)):
-                    m.weight.normal_(mean=0.0, std=0.02)
-                    if getattr(m, "bias", None) is not None:
-                        m.bias.zero_()
+        _bert_init(self.BERT)
         self.device = device
         self.pooling = pooling
         self.version = version
@@ -163,33 +229,9 @@ class TreeBERT(torch.nn.Module):
                                               for _, n in _LAYER_FIELDS]
 
     def _bind(self, dev):
-        """The argument struct, refilled only when a parameter was rebound, moved or (a tensor the
-        kernels cannot read in place: not fp32 / contiguous / 16-byte aligned / on ``dev``) changed."""
-        by_name = dict(self.named_parameters())
-        src = [by_name[n] for n in self.names()]
-        direct = [t.dtype == torch.float32 and t.is_contiguous() and t.device == dev and t.data_ptr() % 16 == 0
-                  for t in src]
-        key = (dev,) + tuple((t.data_ptr(), t.dtype, None if ok else t._version) for t, ok in zip(src, direct))
-        st = self.__dict__.get("_state")
-        if st is not None and st["key"] == key:
-            return st
-        held = [t.detach() if ok else t.detach().to(device=dev, dtype=torch.float32).contiguous().clone()
-                for t, ok in zip(src, direct)]
-        a = _lib.BertArgs()
-        it = iter(held)
-        for field, _ in _TOP_FIELDS:
-            setattr(a, field, next(it).data_ptr())
-        for i in range(self.num_layers):
-            for field, _ in _LAYER_FIELDS:
-                setattr(a.layer[i], field, next(it).data_ptr())
-        a.hidden, a.heads, a.intermediate, a.num_layers = self.hidden, self.heads, self.intermediate, self.num_layers
-        a.max_pos, a.out_feats, a.ln_eps = self.max_pos, self.num_classes, LN_EPS
-        if st is None or st["status"].device != dev:
-            st = {"status": torch.zeros(1, dtype=torch.int32, device=dev),
-                  "seen": torch.zeros(1, dtype=torch.int32, device=dev), "sizes": {}, "ws": {}}
-            self.__dict__["_state"] = st
-        a.status = st["status"].data_ptr()
-        st.update(key=key, args=a, held=held)
+        """The argument struct (:func:`_bind_weights`), refilled only when a parameter changed."""
+        st = _bind_weights(self, self.names(), _TOP_FIELDS, dev, _lib.BertArgs)
+        st["args"].out_feats = self.num_classes
         return st
 
     # ---- bf16 weight images of the root-only chain
@@ -272,19 +314,11 @@ class TreeBERT(torch.nn.Module):
     def _workspace(self, st, N, B, full, dev):
         """The form's workspace, asked for again only when ``(N, B)`` changes; never shrinks.  ``full``:
         True, False, or ``"w16"`` (the root-only form on weight images)."""
-        if st["sizes"].get(full) != (N, B):
+        def need():
             if full == "w16":
-                need = _lib.lib().bgcn_bert_w16_workspace_size(B, self.hidden, self.intermediate, self.num_layers)
-            else:
-                need = _lib.lib().bgcn_bert_workspace_size(N, B, self.hidden, self.intermediate, self.num_layers,
-                                                           int(full))
-            if need == 0:
-                raise _lib.BGCNError("bgcn_bert_eval: unsupported shape (hidden = 64 heads in [64, 1024], intermediate "
-                                     "% 64 in [64, 4096], num_layers in [1, 24])")
-            if st["ws"].get(full) is None or st["ws"][full].numel() < need or st["ws"][full].device != dev:
-                st["ws"][full] = _lib.workspace(need, dev)
-            st["sizes"][full] = (N, B)
-        return st["ws"][full]
+                return _lib.lib().bgcn_bert_w16_workspace_size(B, self.hidden, self.intermediate, self.num_layers)
+            return _lib.lib().bgcn_bert_workspace_size(N, B, self.hidden, self.intermediate, self.num_layers, int(full))
+        return _grow_workspace(st, full, (N, B), need, "bgcn_bert_eval", dev)
 
     def _run(self, x, rootindex, y=None, logp=None, want_pred=False, want_hidden=False, want_sums=False, hidden=None):
         if not x.is_cuda:
@@ -361,15 +395,8 @@ class TreeBERT(torch.nn.Module):
         y = y.to(device=dev, dtype=torch.int64).contiguous()
         if y.numel() != B:
             raise ValueError("y must have one label per tree")
-        if st["sizes"].get(form) != B:
-            need = getattr(_lib.lib(), size_fn)(N, B, self.hidden, self.intermediate, self.num_layers)
-            if need == 0:
-                raise _lib.BGCNError(f"{grad_fn}: unsupported shape (hidden = 64 heads in [64, 1024], "
-                                     "intermediate % 64 in [64, 4096], num_layers in [1, 24])")
-            if st["ws"].get(form) is None or st["ws"][form].numel() < need or st["ws"][form].device != dev:
-                st["ws"][form] = _lib.workspace(need, dev)
-            st["sizes"][form] = B
-        ws = st["ws"][form]
+        ws = _grow_workspace(st, form, B, lambda: getattr(_lib.lib(), size_fn)(N, B, self.hidden, self.intermediate,
+                                                                            self.num_layers), grad_fn, dev)
         r = {"logp": torch.empty(B, C, dtype=torch.float32, device=dev),
              "loss": torch.empty(1, dtype=torch.float32, device=dev),
              "correct": torch.empty(1, dtype=torch.int32, device=dev),
@@ -534,12 +561,7 @@ class TreeBERT(torch.nn.Module):
         """One host sync: raise ``IndexError`` when any batch evaluated since the last check held a
         ``rootindex`` that does not increase strictly or lies outside ``[0, N)``, a tree longer than
         ``max_pos``, or a label outside ``[0, num_classes)``."""
-        st = self.__dict__.get("_state")
-        if st is None:
-            return
-        s = int(st["seen"].item())
-        st["seen"].zero_()
-        if s & _lib.BGCN_STATUS_SEQUENCE:
+        if _take_seen(self) & _lib.BGCN_STATUS_SEQUENCE:
             raise IndexError("the batch holds a rootindex that does not increase strictly or is out of range, "
                              "a tree longer than max_pos, or a label outside [0, num_classes)")
 
@@ -688,3 +710,132 @@ class TreeBERTTrainStep:
                                    "label outside [0, num_classes))",
                         suffix=f" ({self.last_skipped} updates skipped)")
         return self.last_skipped
+
+
+# bgcn_bert_encode_args' top-level weights: BertModel's own names (TreeBERT's without "BERT." and fc)
+_ENC_TOP_FIELDS = (("word_emb", "embeddings.word_embeddings.weight"),) + tuple(
+    (f, n[len("BERT."):]) for f, n in _TOP_FIELDS if n.startswith("BERT."))
+
+
+class TweetEncoder(torch.nn.Module):
+    """The feature extraction of the PHEME study (``Process/getPHEMEgraph.py:104-118``): a plain
+    ``BertModel`` in eval mode over token ids - not a decoder and no attention mask, so every position
+    of a tweet, padding included, attends to every other - as one native call (``bgcn_bert_encode``)
+    per tree of tweets::
+
+        embeddings = model.embeddings(input_ids)          # [n, T, hidden] -> x, root
+        cls = model(input_ids).pooler_output              # [n, hidden]    -> cls
+
+    The module holds ``BertModel``'s parameters under its own names (``embeddings.word_embeddings.weight``
+    ... ``pooler.dense.bias``), so ``BertModel.state_dict()`` loads with ``strict=True``.  The tokenizer
+    and the pretrained weights stay with the caller: ``transformers`` is not imported and nothing is
+    downloaded.  Initialisation is BERT's (normal with std 0.02).  The parameters are read in place, fp32;
+    there is no autograd path.
+
+    ``pooler_output`` reads position 0 of the last layer only, so by default that layer runs on the
+    ``[n, hidden]`` first rows (its keys and values on all rows): exact, like the root-only form of
+    :class:`TreeBERT`.  Asking for ``last_hidden_state`` runs it on every row."""
+
+    def __init__(self, hidden=768, heads=12, intermediate=3072, num_layers=12, max_pos=512, vocab=30522, device=None,
+                 _holders=None):
+        super().__init__()
+        self.hidden, self.heads, self.intermediate, self.num_layers = hidden, heads, intermediate, num_layers
+        self.max_pos, self.vocab = max_pos, vocab
+        b = _holders
+        if b is None:
+            b = _bert_holders(hidden, intermediate, num_layers, max_pos, vocab)
+            _bert_init(b)
+        self.embeddings, self.encoder, self.pooler = b.embeddings, b.encoder, b.pooler
+        # a checkpoint written by an older transformers also holds this buffer: dropped on load
+        self._register_load_state_dict_pre_hook(
+            lambda sd, prefix, *_: sd.pop(prefix + "embeddings.position_ids", None))
+        if device is not None:
+            self.to(device)
+
+    @classmethod
+    def from_treebert(cls, model: TreeBERT) -> "TweetEncoder":
+        """An encoder on ``model.BERT``'s parameters: the same tensors (and holder modules), not copies, so
+        a ``load_state_dict``, an optimiser step or a ``.to()`` of either is the other's too."""
+        return cls(model.hidden, model.heads, model.intermediate, model.num_layers, model.max_pos,
+                   model.BERT.embeddings.word_embeddings.num_embeddings, _holders=model.BERT)
+
+    def names(self):
+        """The ``state_dict`` names the native call reads, in the order of its argument struct."""
+        return [n for _, n in _ENC_TOP_FIELDS] + [f"encoder.layer.{i}.{n}" for i in range(self.num_layers)
+                                                  for _, n in _LAYER_FIELDS]
+
+    def _run(self, input_ids, want_cls=True, want_hidden=False, emb=None, cls=None):
+        """One ``bgcn_bert_encode`` call.  ``emb`` / ``cls``: contiguous fp32 ``[n, T, hidden]`` / ``[n, hidden]``
+        tensors to write into (default: new ones); ``want_cls=False``: the embeddings alone."""
+        if not isinstance(input_ids, torch.Tensor) or input_ids.dim() != 2 or input_ids.is_floating_point() \
+                or input_ids.is_complex() or input_ids.dtype == torch.bool:
+            raise ValueError("input_ids must be a 2-D integer tensor [n, T]")
+        n, T = int(input_ids.size(0)), int(input_ids.size(1))
+        if n < 1 or T < 1 or T > self.max_pos:
+            raise ValueError(f"input_ids must hold at least one sequence of 1 to max_pos = {self.max_pos} tokens, "
+                             f"got {tuple(input_ids.shape)}")
+        if not input_ids.is_cuda:
+            raise _lib.BGCNError("bigcn_amd ops take device tensors (no CPU path)")
+        dev = input_ids.device
+        st = _bind_weights(self, self.names(), _ENC_TOP_FIELDS, dev, _lib.BertEncodeArgs)
+        ids = input_ids.to(torch.int64).contiguous()
+        H = self.hidden
+        if emb is None:
+            emb = torch.empty(n, T, H, dtype=torch.float32, device=dev)
+        if cls is None and want_cls:
+            cls = torch.empty(n, H, dtype=torch.float32, device=dev)
+        hid = torch.empty(n, T, H, dtype=torch.float32, device=dev) if want_hidden else None
+        a = st["args"]
+        a.input_ids, a.num_seqs, a.seq_len, a.vocab = ids.data_ptr(), n, T, self.vocab
+        a.embeddings, a.ld_embeddings, a.cls, a.hidden_out = emb.data_ptr(), H, ptr(cls), ptr(hid)
+        a.last_layer_full, a.embed_only = int(want_hidden), int(not want_cls)
+        ws = None
+        if want_cls:
+            ws = _grow_workspace(st, "encode", (n, T), lambda: _lib.lib().bgcn_bert_encode_workspace_size(
+                n, T, H, self.intermediate, self.num_layers, int(want_hidden)), "bgcn_bert_encode", dev)
+        check(_lib.lib().bgcn_bert_encode(ctypes.addressof(a), ptr(ws), 0 if ws is None else ws.numel(), stream_handle()))
+        st["seen"].bitwise_or_(st["status"])   # the call zeroes its status word; check_status reads this one
+        return emb, cls, hid
+
+    def encode(self, input_ids, return_hidden=False):
+        """``(embeddings [n, T, hidden], cls [n, hidden])`` of the ``n`` sequences ``input_ids [n, T]``
+        (integer ids on the GPU; int32 is converted): ``model.embeddings(input_ids)`` and
+        ``model(input_ids).pooler_output``.  ``return_hidden=True`` also returns ``last_hidden_state
+        [n, T, hidden]`` and runs the last layer on every row.  New tensors on every call, no host sync;
+        a token id outside ``[0, vocab)`` is flagged (:meth:`check_status`), never read out of bounds."""
+        emb, cls, hid = self._run(input_ids, want_hidden=return_hidden)
+        return (emb, cls, hid) if return_hidden else (emb, cls)
+
+    def embed(self, input_ids):
+        """``model.embeddings(input_ids)`` alone, ``[n, T, hidden]``: no encoder layer runs."""
+        return self._run(input_ids, want_cls=False)[0]
+
+    def forward(self, input_ids):
+        """:meth:`encode`."""
+        return self.encode(input_ids)
+
+    def features(self, input_ids, max_seqs=64, root_index=0):
+        """The arrays ``getPHEMEgraph.py:116-118`` stores for one tree of ``n`` tweets, as device tensors:
+        ``{"x": [n, T * hidden], "cls": [n, hidden], "root": x[root_index : root_index + 1]}``.  A tree of
+        more than ``max_seqs`` tweets goes through several calls (the sequences are independent), each
+        writing its rows of the one preallocated result; the workspace is that of ``max_seqs`` tweets."""
+        if max_seqs < 1:
+            raise ValueError("max_seqs must be at least 1")
+        if not isinstance(input_ids, torch.Tensor) or input_ids.dim() != 2 or input_ids.size(0) < 1:
+            raise ValueError("input_ids must be a 2-D integer tensor [n, T]")
+        if not input_ids.is_cuda:
+            raise _lib.BGCNError("bigcn_amd ops take device tensors (no CPU path)")
+        n, T = int(input_ids.size(0)), int(input_ids.size(1))
+        if not 0 <= root_index < n:
+            raise IndexError("root_index out of range")
+        x = torch.empty(n, T, self.hidden, dtype=torch.float32, device=input_ids.device)
+        cls = torch.empty(n, self.hidden, dtype=torch.float32, device=input_ids.device)
+        for i in range(0, n, max_seqs):
+            self._run(input_ids[i:i + max_seqs], emb=x[i:i + max_seqs], cls=cls[i:i + max_seqs])
+        x = x.view(n, T * self.hidden)
+        return {"x": x, "cls": cls, "root": x[root_index:root_index + 1]}
+
+    def check_status(self) -> None:
+        """One host sync: raise ``IndexError`` when any call since the last check read a token id outside
+        ``[0, vocab)``."""
+        raise_on_status(_take_seen(self), bits=_lib.BGCN_STATUS_TOKEN)

@@ -56,4 +56,14 @@ void bert_setup(const bgcn_bert_args* a, SeqInfo sq, int64_t* first, hipStream_t
 // seq_finish
 int bert_head(const bgcn_bert_args* a, const float* P, float* loss_row, int32_t* predw, hipStream_t s);
 
+// The two row kernels between the GEMMs (bgcn_bert.hip), also launched by the encoder over token ids
+// (bgcn_bert_encode.hip).
+// k_bert_add_ln: out[r] = LN(y[r] + bias + res[r]) over M rows of H columns, one wave per row; y and
+// out have the row stride H, res the row stride ldres.  rowsum [M] and first [1] (rows below *first
+// become zeros) may be null.
+void bert_add_ln(const float* y, const float* bias, const float* res, int64_t ldres, const float* g, const float* be,
+                 float* out, float* rowsum, const int64_t* first, int64_t M, int H, float eps, hipStream_t s);
+// k_bert_bias_act: y[r][c] = act(y[r][c] + bias[c]) in place over [M, C], C % 4 == 0; gelu: the erf form
+void bert_bias_act(float* y, const float* bias, int64_t M, int64_t C, bool gelu, hipStream_t s);
+
 }  // namespace bgcn

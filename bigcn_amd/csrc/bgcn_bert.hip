@@ -116,14 +116,15 @@ __global__ __launch_bounds__(256) void k_bert_embed(EmbedArgs a) {
   ln_row(v, per, H, a.g, a.be, a.eps, l, dst, nullptr);
 }
 
-// ---- out[r] = LN(y[r] + bias + res[r]), one wave per row.  The last layer of the full form also
-// writes the row's sum and zero rows above the first sequence (first, rowsum: null elsewhere).
+// ---- out[r] = LN(y[r] + bias + res[r]), one wave per row (res: rows ldres floats apart).  The last
+// layer of the full form also writes the row's sum and zero rows above the first sequence (first,
+// rowsum: null elsewhere).
 struct AddLnArgs {
   const float *y, *bias, *res, *g, *be;
   float* out;
   float* rowsum;
   const int64_t* first;
-  int64_t M;
+  int64_t M, ldres;
   int H;
   float eps;
 };
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(256) void k_bert_add_ln(AddLnArgs a) {
     if (a.rowsum && l == 0) a.rowsum[r] = 0.f;
     return;
   }
-  const float *y = a.y + r * H, *res = a.res + r * H;
+  const float *y = a.y + r * H, *res = a.res + r * a.ldres;
   float v[kMaxPer];
 #pragma unroll
   for (int i = 0; i < kMaxPer; ++i)
@@ -419,6 +420,21 @@ struct BertWs {
 
 }  // namespace
 
+void bert_add_ln(const float* y, const float* bias, const float* res, int64_t ldres, const float* g, const float* be,
+                 float* out, float* rowsum, const int64_t* first, int64_t M, int H, float eps, hipStream_t s) {
+  AddLnArgs a{y, bias, res, g, be, out, rowsum, first, M, ldres, H, eps};
+  hipLaunchKernelGGL(k_bert_add_ln, dim3(grid_for(M, 4)), dim3(256), 0, s, a);
+}
+
+void bert_bias_act(float* y, const float* bias, int64_t M, int64_t C, bool gelu, hipStream_t s) {
+  const int64_t total4 = M * C / 4;
+  const dim3 grid(unsigned(std::min<int64_t>((total4 + 255) / 256, 4096)));
+  if (gelu)
+    hipLaunchKernelGGL(k_bert_bias_act<true>, grid, dim3(256), 0, s, y, bias, total4, int(C / 4));
+  else
+    hipLaunchKernelGGL(k_bert_bias_act<false>, grid, dim3(256), 0, s, y, bias, total4, int(C / 4));
+}
+
 bool bert_shape_ok(int64_t N, int64_t B, int64_t H, int64_t I, int64_t L) {
   return N > 0 && B > 0 && N < (int64_t(1) << 31) - 1 && B <= 65535 && H % kHeadDim == 0 && H >= 64 &&
          H <= kMaxHidden && I % 64 == 0 && I >= 64 && I <= 4096 && L >= 1 && L <= BGCN_BERT_MAX_LAYERS;
@@ -487,14 +503,12 @@ static int bert_eval_impl(const bgcn_bert_args* a, void* ws, size_t ws_bytes, hi
   BGCN_CHECK_ARG(ws && align_up(c.off, 256) <= ws_bytes, "workspace too small");   // bgcn_bert_workspace_size's figure
   const int64_t M = full ? N : B;
   const int heads = int(a->heads);
-  const unsigned rows4 = grid_for(M, 4);
 
   bert_setup(a, w.sq, w.first, s);
   EmbedArgs em{a->x, a->ldx, a->pos_emb, a->type_emb, a->emb_ln_w, a->emb_ln_b, w.sq, w.h, int(H), a->ln_eps, full ? 0 : 1};
   hipLaunchKernelGGL(k_bert_embed, dim3(unsigned(B), full ? grid_for(a->max_pos, 4) : 1), dim3(256), 0, s, em);
   BGCN_CHECK_LAUNCH();
 
-  const auto bias_grid = [](int64_t total4) { return dim3(unsigned(std::min<int64_t>((total4 + 255) / 256, 4096))); };
   for (int l = 0; l < L; ++l) {
     const bgcn_bert_layer& y = a->layer[l];
     const bool last = l == L - 1;
@@ -509,21 +523,17 @@ static int bert_eval_impl(const bgcn_bert_args* a, void* ws, size_t ws_bytes, hi
                            N, heads, a->attn_sum);
     } else {   // P = 1 at position 0: ctx = v
       BGCN_TRY(gemm_xwt_impl(w.h, H, y.v_w, nullptr, H, H, w.ctx, H, M, H, H, s, nullptr));
-      hipLaunchKernelGGL(k_bert_bias_act<false>, bias_grid(M * H / 4), dim3(256), 0, s, w.ctx, y.v_b, M * H / 4,
-                         int(H / 4));
+      bert_bias_act(w.ctx, y.v_b, M, H, false, s);
     }
     BGCN_CHECK_LAUNCH();
     BGCN_TRY(gemm_xwt_impl(w.ctx, H, y.ao_w, nullptr, H, H, w.t, H, M, H, H, s, nullptr));
-    AddLnArgs l1{w.t, y.ao_b, w.h, y.ao_ln_w, y.ao_ln_b, w.a, nullptr, nullptr, M, int(H), a->ln_eps};
-    hipLaunchKernelGGL(k_bert_add_ln, dim3(rows4), dim3(256), 0, s, l1);
+    bert_add_ln(w.t, y.ao_b, w.h, H, y.ao_ln_w, y.ao_ln_b, w.a, nullptr, nullptr, M, int(H), a->ln_eps, s);
     BGCN_TRY(gemm_xwt_impl(w.a, H, y.i_w, nullptr, H, I, w.inter, I, M, I, H, s, nullptr));
-    hipLaunchKernelGGL(k_bert_bias_act<true>, bias_grid(M * I / 4), dim3(256), 0, s, w.inter, y.i_b, M * I / 4,
-                       int(I / 4));
+    bert_bias_act(w.inter, y.i_b, M, I, true, s);
     BGCN_TRY(gemm_xwt_impl(w.inter, I, y.o_w, nullptr, I, H, w.t, H, M, H, I, s, nullptr));
     const bool fin = full && last;
-    AddLnArgs l2{w.t, y.o_b, w.a, y.o_ln_w, y.o_ln_b, fin && a->hidden_out ? a->hidden_out : w.h,
-                 fin ? a->hidden_sum : nullptr, fin ? w.first : nullptr, M, int(H), a->ln_eps};
-    hipLaunchKernelGGL(k_bert_add_ln, dim3(rows4), dim3(256), 0, s, l2);
+    bert_add_ln(w.t, y.o_b, w.a, H, y.o_ln_w, y.o_ln_b, fin && a->hidden_out ? a->hidden_out : w.h,
+                fin ? a->hidden_sum : nullptr, fin ? w.first : nullptr, M, int(H), a->ln_eps, s);
     BGCN_CHECK_LAUNCH();
   }
 

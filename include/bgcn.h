@@ -1532,6 +1532,81 @@ size_t bgcn_bert_train_skinny_workspace_size(int64_t num_nodes, int64_t num_seqs
 int bgcn_bert_train_grad_skinny(const bgcn_bert_train_args* args, void* workspace, size_t workspace_bytes,
                                 bgcn_stream_t stream);
 
+/* --------------------------------------------------------------------------
+ * PHEME feature extraction: the bidirectional BERT encoder over token ids
+ * (Process/getPHEMEgraph.py:104-118) for a whole tree of tweets as one launch sequence: no host
+ * round trip, no allocation (everything lives in the caller's workspace).  Additive entry points:
+ * BGCN_ABI_VERSION is unchanged.
+ *
+ * The model is a plain BertModel in eval mode: not a decoder and no attention mask, so every one of
+ * the seq_len positions of a sequence, padding included, attends to every other.  Sequence b is the
+ * row b of input_ids [num_seqs, seq_len] (int64), its token t at position t, row b seq_len + t of
+ * every [num_seqs seq_len, .] matrix below:
+ *   embeddings  h = LN(word_embeddings[id] + token_type_embeddings[0] + position_embeddings[t])
+ *               (biased variance, eps = ln_eps): model.embeddings(input_ids), the array x / root
+ *   per layer   q, k, v = Linear(h); per head (width 64): P = softmax(q k^T / 8) over all seq_len
+ *               keys, ctx = P v;  a = LN(dense(ctx) + h);  o = LN(dense2(gelu(dense1(a))) + a),
+ *               gelu(x) = x 0.5 (1 + erf(x / sqrt 2))
+ *   cls         tanh(pooler.dense(o_last[0])): model(input_ids).pooler_output
+ * Arithmetic: fp32 throughout, the GEMMs of bgcn_bert_eval (which change kernel at 8192 rows: the
+ * results of two calls with another num_seqs seq_len agree within fp32 rounding, not bit for bit).
+ * Attention is one pass over the key tiles with a running maximum and a rescaled sum, on the fp32
+ * MFMA; keys past seq_len in the last tile add exactly 0 to the normaliser and to ctx.
+ * Deterministic: no float atomics, fixed summation orders.
+ *
+ * The last layer.  pooler_output reads row 0 of the last layer's output only, so by default
+ * (last_layer_full == 0) the last layer runs k | v over all rows and q, the attention of query 0,
+ * the attention-output dense, the intermediate and output GEMMs and both LayerNorms on the
+ * [num_seqs, hidden] first rows alone: exact, and 10/12 of that layer's GEMM work less.
+ * last_layer_full != 0 runs the last layer on every row; hidden_out (last_hidden_state) needs it.
+ * embed_only != 0: the embeddings alone (required then), no encoder layer; cls may be NULL and no
+ * workspace is read.
+ *
+ * Validity is decided on the device.  *status is zeroed by the call; a token id outside [0, vocab)
+ * sets BGCN_STATUS_TOKEN and is clamped into range before any read, so a flagged call stays in
+ * bounds and finite (the flagged sequence's results are not to be used; the other sequences' are
+ * unchanged).
+ *
+ * BGCN_EINVAL before any HIP call: bgcn_bert_eval's limits on hidden, heads, intermediate and
+ * num_layers with num_seqs seq_len rows and num_seqs <= 65535 ("unsupported shape";
+ * bgcn_bert_encode_workspace_size returns 0 for these), seq_len outside [1, max_pos] or max_pos
+ * over 512, vocab < 1, a null or not 16-byte aligned weight or output (ld_embeddings % 4 != 0 or
+ * below hidden), hidden_out with last_layer_full == 0, "workspace too small".
+ * -------------------------------------------------------------------------- */
+#define BGCN_STATUS_TOKEN 0x200   /* 512: the bit after BGCN_STATUS_SEQUENCE */
+typedef struct bgcn_bert_encode_args {
+  const int64_t* input_ids;      /* [num_seqs, seq_len]                       */
+  int64_t num_seqs;
+  int64_t seq_len;
+  int64_t vocab;                 /* rows of word_emb                          */
+  int64_t hidden;                /* 64 heads                                  */
+  int64_t heads;
+  int64_t intermediate;
+  int64_t num_layers;
+  int64_t max_pos;               /* rows of pos_emb                           */
+  float ln_eps;
+  int32_t reserved;
+  const float* word_emb;         /* [vocab, hidden]                           */
+  const float* pos_emb;          /* [max_pos, hidden]                         */
+  const float* type_emb;         /* [hidden]: token_type_embeddings row 0     */
+  const float* emb_ln_w;         /* [hidden]                                  */
+  const float* emb_ln_b;
+  bgcn_bert_layer layer[BGCN_BERT_MAX_LAYERS];
+  const float* pooler_w;         /* [hidden, hidden]                          */
+  const float* pooler_b;
+  float* embeddings;             /* [num_seqs seq_len, ld_embeddings], or NULL */
+  int64_t ld_embeddings;
+  float* cls;                    /* [num_seqs, hidden] pooler_output          */
+  float* hidden_out;             /* [num_seqs seq_len, hidden] last_hidden_state, or NULL */
+  int32_t* status;               /* [1]                                       */
+  int32_t last_layer_full;       /* != 0: the last layer on every row         */
+  int32_t embed_only;            /* != 0: embeddings only, no encoder layer   */
+} bgcn_bert_encode_args;
+size_t bgcn_bert_encode_workspace_size(int64_t num_seqs, int64_t seq_len, int64_t hidden, int64_t intermediate,
+                                       int64_t num_layers, int last_layer_full);
+int bgcn_bert_encode(const bgcn_bert_encode_args* args, void* workspace, size_t workspace_bytes,
+                     bgcn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
